@@ -13,6 +13,11 @@ timed region starts.
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
 
+A plain run sets up, warms up, times EXACTLY K steps in one timed region, writes the arrays of its last step if
+--dump-outputs DIR is given and prints the line.  Everything else -- the median of several timed regions, per-phase
+device times and the roofline, the CPU baselines and the chi2 check against the oracle, the end-to-end and growing-graph
+figures, the live PMC traffic and BASELINE configs 3 / 4 / 5 -- runs with --full only.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -86,7 +91,7 @@ def live_traffic(args, budget_s):
             out = os.path.join(tmp, ctr)
             cmd = ["rocprofv3", "--pmc", ctr, "--kernel-trace", "-d", out, "--", sys.executable, os.path.abspath(__file__), "--poses", str(args.poses),
                    "--lookback", str(args.lookback), "--loops", str(args.loops), "--steps", "3", "--warmup", "1", "--cpu-iters", "0", "--phase-reps", "1",
-                   "--repeats", "1", "--other-configs", "0", "--live-traffic", "0", "--extras", "0"]
+                   "--repeats", "1", "--other-configs", "0", "--live-traffic", "0", "--extras", "0", "--full"]
             pr = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
             left = budget_s - (time.perf_counter() - t0)
             try:
@@ -129,7 +134,7 @@ def other_configs(budget_s):
         ("cfg4_vio", "VIO: 50 000 key frames, CombinedImuFactor + BetweenFactor<Pose3> + OrientedPlane3Factor (200 planes), GTSAM-semantics LM",
          [sys.executable, tool, "vio", "--kf", "50000", "--iters", "3"], 90),
         ("cfg5_1m_one_gpu", "1M-pose / 10M-edge SE3 pose graph (seed 45) on ONE MI355X (the 8-GPU configuration's graph)",
-         [sys.executable, os.path.abspath(__file__), "--poses", "1000000", "--steps", "3", "--warmup", "1", "--cpu-iters", "0", "--repeats", "1", "--other-configs", "0", "--extras", "0"], 120),
+         [sys.executable, os.path.abspath(__file__), "--poses", "1000000", "--steps", "3", "--warmup", "1", "--cpu-iters", "0", "--repeats", "1", "--other-configs", "0", "--extras", "0", "--full"], 120),
     ]
     res, t_all = {}, time.perf_counter()
     for key, what, cmd, tmo in jobs:
@@ -178,6 +183,22 @@ def other_configs(budget_s):
     return res
 
 
+DUMP_MAX_ROWS = 1000000        # 56 MB of float64 poses: the dump stays under 64 MB
+
+
+def dump_outputs(path, gr, chi2):
+    """what the timed path hands its caller after its last step: every pose (x y z qx qy qz qw, float64) and the final chi2;
+    above DUMP_MAX_ROWS poses a fixed seeded sample of rows (pose_index.npy says which, in ascending order)"""
+    os.makedirs(path, exist_ok=True)
+    poses = np.ascontiguousarray(gr.get_poses(), dtype=np.float64)
+    if len(poses) > DUMP_MAX_ROWS:
+        idx = np.sort(np.random.default_rng(0).choice(len(poses), DUMP_MAX_ROWS, replace=False))
+        poses = poses[idx]
+        np.save(os.path.join(path, "pose_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "poses.npy"), poses)
+    np.save(os.path.join(path, "chi2.npy"), np.array([chi2], dtype=np.float64))
+
+
 def pose_compose(a, b):
     """a * b for poses t(3) q(4: x y z w)"""
     ax, ay, az, aw = a[3:]
@@ -199,9 +220,17 @@ def main():
     ap.add_argument("--lookback", type=int, default=5)
     ap.add_argument("--loops", type=int, default=4)
     ap.add_argument("--seed", type=int, default=-1, help="generator seed (default: 42, the configuration the metric is quoted on; 45 for --poses 1000000)")
-    ap.add_argument("--cpu-iters", type=int, default=3, help="oracle iterations for cpu_baseline (0 = skip)")
-    ap.add_argument("--phase-reps", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=-1, help="timed regions (each: fresh context, W warm-up + exactly K timed iterations); the median is reported.  Default: 5 on one GPU up to 200k poses, 1 otherwise")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: several timed regions (--repeats), per-phase device times and "
+                         "the roofline, cpu_baseline and the final-chi2 check against the oracle, end_to_end / end_to_end_growing_graph, the live "
+                         "PMC traffic and other_configs.  Off by default: a plain run times exactly --steps steps in one region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed to DIR/<name>.npy: poses.npy (float64, one row per "
+                         "pose: x y z qx qy qz qw; a fixed seeded sample of 1M rows, with pose_index.npy, above 1M poses) and chi2.npy "
+                         "(float64 [final chi2])")
+    ap.add_argument("--cpu-iters", type=int, default=3, help="--full: oracle iterations for cpu_baseline (0 = skip)")
+    ap.add_argument("--phase-reps", type=int, default=5, help="--full: repetitions of each phase for the per-phase device times")
+    ap.add_argument("--repeats", type=int, default=-1, help="timed regions (each: fresh context, W warm-up + exactly K timed iterations); the median is reported.  Default: 1; with --full 5 on one GPU up to 200k poses")
     ap.add_argument("--replicas", action="store_true",
                     help="N > 1: N independent copies of the graph, no collective (aggregate replica throughput, weak scaling) "
                          "instead of the default: ONE graph, distributed factorisation over the N GPUs (strong scaling)")
@@ -209,13 +238,13 @@ def main():
                     help="collectives of the distributed mode: RCCL enqueued on libfgo's stream (default when the torch backend "
                          "is nccl), or torch.distributed.all_reduce through the host-callback hook")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for 1-GPU smoke tests)")
-    ap.add_argument("--extras", type=int, default=1, help="0: skip the end-to-end and growing-graph figures (the PMC passes of --live-traffic run the script this way)")
+    ap.add_argument("--extras", type=int, default=1, help="--full, 0: skip the end-to-end and growing-graph figures (the PMC passes of --live-traffic run the script this way)")
     ap.add_argument("--extras-budget", type=float, default=200.0, help="seconds of wall clock that --live-traffic and --other-configs may take together; what does not fit is left out and says so")
     ap.add_argument("--live-traffic", type=int, default=-1,
-                    help="1: measure roofline.traffic NOW with two rocprofv3 --pmc passes of a short run of this script (about a minute); 0: report the "
+                    help="--full, 1: measure roofline.traffic NOW with two rocprofv3 --pmc passes of a short run of this script (about a minute); 0: report the "
                          "committed measurement (profiles/pmc_traffic_cfg2.json); default: on for the default 1-GPU headline workload")
     ap.add_argument("--other-configs", type=int, default=-1,
-                    help="1: after the headline's timed regions also run BASELINE configs 3 (BA), 4 (VIO) and 5 (1M poses on this one GPU) at full size, each in "
+                    help="--full, 1: after the headline's timed regions also run BASELINE configs 3 (BA), 4 (VIO) and 5 (1M poses on this one GPU) at full size, each in "
                          "its own process, and report them under `other_configs` (never in `value`); default: on for the default 1-GPU headline workload")
     args = ap.parse_args()
 
@@ -337,10 +366,11 @@ def main():
             dt = float(t.item())
         return gr, chi0, sst, st, dt
 
-    # the timed region is ~0.15 s; it is repeated from the same start (fresh context each time) and the
-    # MEDIAN repeat is reported (every repeat is listed), which is steadier box to box than a single 20-step region
+    # the timed region is ~0.15 s; with --full it is repeated from the same start (fresh context each time)
+    # and the MEDIAN repeat is reported (every repeat is listed), which is steadier box to box than a single 20-step region.
+    # A plain run times one region of exactly --steps steps: the caller sizes --steps by ms_per_step
     if args.repeats < 0:
-        args.repeats = 5 if (world == 1 and args.poses <= 200000) else 1
+        args.repeats = 5 if (args.full and world == 1 and args.poses <= 200000) else 1
     runs = []
     for rep in range(max(1, args.repeats)):
         r = timed_region()
@@ -356,14 +386,17 @@ def main():
     trial_ms = st.reserved[0] / max(trials, 1)                      # device time per LM trial (HIP events on libfgo's stream)
     xgmi_per_trial = st.reserved[2] / max(trials, 1)                 # bytes this rank handed to the collectives, per trial
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gr, chi_final)
+
     # per-phase device times (HIP events on the library's stream): single-GPU contexts only
-    ms = {p: gr.bench_phase(p, args.phase_reps) for p in (0, 1, 2)} if (rank == 0 and not shard) else None
+    ms = {p: gr.bench_phase(p, args.phase_reps) for p in (0, 1, 2)} if (args.full and rank == 0 and not shard) else None
 
     # end to end as the reference's driver pays it (g2o/g2o_graph.cpp:241-252 after vertices arrived: structure rebuilt, then
     # 10 x optimize(2)): graph hand-over through the C-ABI + structure phase + upload + 20 iterations, wall clock.  Reported
     # next to `value`, never as `value` (the structure phase is timed separately).
     e2e = None
-    if world == 1 and args.poses <= 200000 and args.extras:
+    if args.full and world == 1 and args.poses <= 200000 and args.extras:
         sync()
         t0 = time.perf_counter()
         g3 = fresh()
@@ -384,7 +417,7 @@ def main():
     # (g2o/g2o_graph.cpp:159-239), so the far loop closures the generator attaches to the NEW vertices are left out here.  g2o
     # rebuilds its structure at every call; libfgo in growth mode (fgo_set_growth) extends the resident structure in place.
     growth = None
-    if world == 1 and args.poses <= 200000 and args.poses >= 2000 and args.extras:
+    if args.full and world == 1 and args.poses <= 200000 and args.poses >= 2000 and args.extras:
         n_steps, step = 5, 10
         n0 = n - n_steps * step
         old = g["ej"] < n0
@@ -453,50 +486,52 @@ def main():
     out = None
     if rank == 0:
         value = (1 if shard else world) * args.steps / dt
-        # ---- roofline of the dominant phase, measured live with HIP events on the library's stream
-        # phase 1 is what a trial runs: the level-by-level factor sweep with the forward solve fused in (the right-hand
-        # side rides along as one more matrix row); phase 2 is the backward sweep
-        names = {0: "k_linearize", 1: "factor sweep + fused forward solve (k_chol_leaf, k_chol_acc, k_panel_tri, k_panel_rows)",
-                 2: "backward solve sweep (k_solve_bwd, k_bwd_ext, k_bwd_tri)"}
-        bytes_ = {0: sst.bytes_linearize, 1: sst.bytes_factor, 2: sst.bytes_solve}
-        if ms is None:
-            # distributed: the phases are interleaved with collectives, so the roofline is taken over the whole LM trial:
-            # algorithmic bytes of one trial of the WHOLE graph / device time of a trial / N GPUs = per-GPU achieved rate
-            names = {9: "whole LM trial, distributed over %d GPUs (per-GPU rate)" % world}
-            bytes_ = {9: (sst.bytes_linearize + sst.bytes_factor + sst.bytes_solve) / world}
-            ms = {9: trial_ms}
-        dom = max(ms, key=lambda p: ms[p])
-        achieved = bytes_[dom] / (ms[dom] * 1e-3) / 1e9
-        # HBM bytes of the dominant phase from the PMC counters (FETCH_SIZE / WRITE_SIZE passes, profiles/): a committed
-        # measurement of this exact workload; null for any other size
-        traffic = None
-        traffic_x2 = None
-        traffic_stamp = None
-        try:
-            with open(os.path.join(ROOT, "profiles", "pmc_traffic_cfg2.json")) as fh:
-                pm = json.load(fh)
-            w = pm["workload"]
-            # (... of this exact STRUCTURE: another ordering moves other bytes)
-            same = all(pm.get(k, v) == v for k, v in (("nnz_L_blocks", sst.nnz_L_blocks), ("update_ops", sst.n_update_ops), ("levels", sst.n_levels)))
-            if dom == 1 and (w["poses"], w["lookback"], w["loops"]) == (args.poses, args.lookback, args.loops) and same:
-                traffic = pm["hbm_bytes_per_sweep"]
-                traffic_x2 = pm.get("hbm_bytes_per_sweep_uniform_x2")
-                traffic_stamp = {"measured_at_commit": pm.get("measured_at_commit"), "nnz_L_blocks": pm.get("nnz_L_blocks"), "update_ops": pm.get("update_ops"),
-                                 "levels": pm.get("levels"), "summary": pm.get("summary"),
-                                 "what": "a builder measurement committed with the repo (the driver's run cannot re-measure it); it is reported only while the "
-                                         "structure of this run (blocks of L, block updates, levels) equals the structure it was measured on"}
-        except (OSError, ValueError, KeyError):
+        roofline = None
+        if args.full:
+            # ---- roofline of the dominant phase, measured live with HIP events on the library's stream
+            # phase 1 is what a trial runs: the level-by-level factor sweep with the forward solve fused in (the right-hand
+            # side rides along as one more matrix row); phase 2 is the backward sweep
+            names = {0: "k_linearize", 1: "factor sweep + fused forward solve (k_chol_leaf, k_chol_acc, k_panel_tri, k_panel_rows)",
+                     2: "backward solve sweep (k_solve_bwd, k_bwd_ext, k_bwd_tri)"}
+            bytes_ = {0: sst.bytes_linearize, 1: sst.bytes_factor, 2: sst.bytes_solve}
+            if ms is None:
+                # distributed: the phases are interleaved with collectives, so the roofline is taken over the whole LM trial:
+                # algorithmic bytes of one trial of the WHOLE graph / device time of a trial / N GPUs = per-GPU achieved rate
+                names = {9: "whole LM trial, distributed over %d GPUs (per-GPU rate)" % world}
+                bytes_ = {9: (sst.bytes_linearize + sst.bytes_factor + sst.bytes_solve) / world}
+                ms = {9: trial_ms}
+            dom = max(ms, key=lambda p: ms[p])
+            achieved = bytes_[dom] / (ms[dom] * 1e-3) / 1e9
+            # HBM bytes of the dominant phase from the PMC counters (FETCH_SIZE / WRITE_SIZE passes, profiles/): a committed
+            # measurement of this exact workload; null for any other size
             traffic = None
-        roofline = {"bound": "hbm", "kernel": names[dom], "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_uniform_x2": traffic_x2, "traffic_stamp": traffic_stamp,
-                    "traffic_note": "PMC FETCH_SIZE / WRITE_SIZE of this workload, FETCH_SIZE corrected per access pattern on known byte counts (profiles/r04_b_pmc_calibration.txt); uniform_x2 = every kernel x2 (upper bound)",
-                    "algorithmic_bytes_per_pass": bytes_[dom], "ms_per_pass": ms[dom],
-                    "phases_ms": {names[p]: ms[p] for p in ms},
-                    "phases_GBs": {names[p]: bytes_[p] / (ms[p] * 1e-3) / 1e9 for p in ms}}
+            traffic_x2 = None
+            traffic_stamp = None
+            try:
+                with open(os.path.join(ROOT, "profiles", "pmc_traffic_cfg2.json")) as fh:
+                    pm = json.load(fh)
+                w = pm["workload"]
+                # (... of this exact STRUCTURE: another ordering moves other bytes)
+                same = all(pm.get(k, v) == v for k, v in (("nnz_L_blocks", sst.nnz_L_blocks), ("update_ops", sst.n_update_ops), ("levels", sst.n_levels)))
+                if dom == 1 and (w["poses"], w["lookback"], w["loops"]) == (args.poses, args.lookback, args.loops) and same:
+                    traffic = pm["hbm_bytes_per_sweep"]
+                    traffic_x2 = pm.get("hbm_bytes_per_sweep_uniform_x2")
+                    traffic_stamp = {"measured_at_commit": pm.get("measured_at_commit"), "nnz_L_blocks": pm.get("nnz_L_blocks"), "update_ops": pm.get("update_ops"),
+                                     "levels": pm.get("levels"), "summary": pm.get("summary"),
+                                     "what": "a builder measurement committed with the repo (the driver's run cannot re-measure it); it is reported only while the "
+                                             "structure of this run (blocks of L, block updates, levels) equals the structure it was measured on"}
+            except (OSError, ValueError, KeyError):
+                traffic = None
+            roofline = {"bound": "hbm", "kernel": names[dom], "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_uniform_x2": traffic_x2, "traffic_stamp": traffic_stamp,
+                        "traffic_note": "PMC FETCH_SIZE / WRITE_SIZE of this workload, FETCH_SIZE corrected per access pattern on known byte counts (profiles/r04_b_pmc_calibration.txt); uniform_x2 = every kernel x2 (upper bound)",
+                        "algorithmic_bytes_per_pass": bytes_[dom], "ms_per_pass": ms[dom],
+                        "phases_ms": {names[p]: ms[p] for p in ms},
+                        "phases_GBs": {names[p]: bytes_[p] / (ms[p] * 1e-3) / 1e9 for p in ms}}
         cpu = None
         chi_rel = None
         chi_rel_detail = None
-        if world == 1 and args.cpu_iters > 0:
+        if args.full and world == 1 and args.cpu_iters > 0:
             # ---- CPU baseline: the oracle (g2o-semantics port) on the SAME graph, bounded sample, timed on this box's cores
             #      by a binary built ON this box (-march=native; VERDICT r3 weak #4: the shipped checker is a portable build)
             from tests import orc_binding as orc
@@ -619,7 +654,7 @@ def main():
     gr.close()
     extras_used = 0.0
     t_main1 = time.perf_counter()
-    if out is not None and world == 1 and out["roofline"].get("kernel", "").startswith("factor sweep") and \
+    if out is not None and args.full and world == 1 and out["roofline"].get("kernel", "").startswith("factor sweep") and \
             (args.live_traffic == 1 or (args.live_traffic < 0 and args.poses == 100000 and args.cpu_iters > 0)):
         t_x = time.perf_counter()
         lt = live_traffic(args, 0.5 * args.extras_budget)
@@ -631,7 +666,7 @@ def main():
             rf["traffic_source"] = "measured by this run"; rf["traffic_measurement"] = {"seconds": lt["seconds"], "how": lt["how"]}
         else:
             rf["traffic_source"] = "committed measurement (the live PMC passes did not complete: see stderr)"
-    if out is not None and world == 1 and (args.other_configs == 1 or (args.other_configs < 0 and args.poses == 100000 and args.cpu_iters > 0)):
+    if out is not None and args.full and world == 1 and (args.other_configs == 1 or (args.other_configs < 0 and args.poses == 100000 and args.cpu_iters > 0)):
         # (this process's contexts are closed: the 1M-pose run wants ~20 GB of its own)
         out["other_configs"] = other_configs(args.extras_budget - extras_used)
     if dist is not None:

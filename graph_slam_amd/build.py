@@ -78,7 +78,16 @@ def build_host(verbose=True):
     return hdir
 
 
+def build_ref(verbose=True):
+    """The reference's own wrappers and drivers, compiled in place into oracle/_ref against the host libraries (test
+    infrastructure, after build_host).  Without the reference tree whatever oracle/_ref already holds is left as it is."""
+    odir = os.path.join(ROOT, "oracle")
+    subprocess.run(["make", "-C", odir, "ref"] + ([] if verbose else ["-s"]), check=True)
+    return os.path.join(odir, "_ref")
+
+
 if __name__ == "__main__":
     build_libfgo(force="--force" in sys.argv)
     build_oracle()
     build_host()
+    build_ref()

@@ -3,10 +3,10 @@ test_ba_imu_graph link unchanged").
 
 graph_slam_amd/host holds no copy or re-typing of the reference's wrappers any more: g2o/g2o_graph.cpp,
 gtsam/gtsam_graph.cpp, gtsam/imu_base.cpp, gtsam/imu_vn100.cpp, gtsam/imu_MEMS.cpp and the three drivers
-g2o/test_g2o_graph.cpp, gtsam/test_vro_imu_graph.cpp, gtsam/test_ba_imu_graph.cpp are compiled IN PLACE from
-/root/reference (when that tree exists: this container) against API slices of g2o / GTSAM that forward to libfgo.so
-(host/shim/g2o, host/shim/gtsam_lite.h, host/fgo_g2o.cpp, host/gtsam_bridge.cpp) plus stand-ins for the un-vendored
-front-end packages.  The built binaries travel to the GPU box like any other in-tree .so.
+g2o/test_g2o_graph.cpp, gtsam/test_vro_imu_graph.cpp, gtsam/test_ba_imu_graph.cpp are compiled IN PLACE from the
+reference tree into oracle/_ref by build() (oracle/Makefile `ref`, where that tree exists) against API slices of g2o /
+GTSAM that forward to libfgo.so (host/shim/g2o, host/shim/gtsam_lite.h, host/fgo_g2o.cpp, host/gtsam_bridge.cpp) plus
+stand-ins for the un-vendored front-end packages.  The built binaries travel with the working tree.
 
 CPU: everything builds and exports the reference's class surface.
 GPU: BASELINE config 1 through the reference's CGraphG2O and through its unmodified driver; the reference's VIO and
@@ -22,19 +22,24 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "graph_slam_amd", "host")
-REF_DRIVER = "/root/reference/g2o/test_g2o_graph.cpp"
+REFBIN = os.path.join(ROOT, "oracle", "_ref")          # the reference's wrappers + drivers, built by build() (oracle/Makefile `ref`)
 
 
 def _make(*targets):
-    return subprocess.run(["make", "-s", "-C", HOST] + list(targets), capture_output=True, text=True)
+    """the host libraries, then the reference-built binaries on top of them (oracle/_ref is left as it is where the
+    reference tree is absent: the binaries built where it exists travel with the tree)"""
+    r = subprocess.run(["make", "-s", "-C", HOST] + list(targets), capture_output=True, text=True)
+    if r.returncode != 0 or targets:
+        return r
+    return subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"], capture_output=True, text=True)
 
 
 def test_host_library_builds_and_exports_surface():
     r = _make()
     assert r.returncode == 0, r.stderr[-2000:]
-    if not os.path.exists(REF_DRIVER) and not os.path.exists(os.path.join(HOST, "libg2o_graph.so")):
+    if not os.path.exists(os.path.join(REFBIN, "libg2o_graph.so")):
         pytest.skip("reference tree not present and no prebuilt wrapper library")
-    out = subprocess.run(["nm", "-DC", os.path.join(HOST, "libg2o_graph.so")], capture_output=True, text=True).stdout
+    out = subprocess.run(["nm", "-DC", os.path.join(REFBIN, "libg2o_graph.so")], capture_output=True, text=True).stdout
     for sym in ["CGraphG2O::CGraphG2O()", "CGraphG2O::createOptimizer()", "CGraphG2O::firstNode(CCameraNode*)",
                 "CGraphG2O::addNode(CCameraNode*)", "CGraphG2O::fakeOdoNode(CCameraNode*)", "CGraphG2O::optimizeGraph()",
                 "CGraphG2O::addToGraph(MatchingResult&, bool)", "CGraphG2O::isSmallTrafo(MatchingResult&)",
@@ -44,12 +49,13 @@ def test_host_library_builds_and_exports_surface():
         assert sym in out, "missing symbol " + sym
 
 
-@pytest.mark.skipif(not os.path.exists(REF_DRIVER), reason="reference tree not present (GPU box)")
 def test_reference_driver_compiles_and_links_unchanged():
-    r = _make("ref_driver_check")
+    r = _make()
     assert r.returncode == 0, r.stderr[-3000:]
+    if "no reference tree" in r.stdout and not os.path.exists(os.path.join(REFBIN, "libg2o_graph.so")):
+        pytest.skip("reference tree not present and no prebuilt oracle/_ref")
     for b in ("_ref_test_g2o_graph", "_ref_test_vro_imu_graph", "_ref_test_ba_imu_graph", "libg2o_graph.so", "libgtsam_graph.so"):
-        assert os.path.exists(os.path.join(HOST, b)), b
+        assert os.path.exists(os.path.join(REFBIN, b)), b
 
 
 def _oracle_schedule(n, lookback):
@@ -68,7 +74,7 @@ def _oracle_schedule(n, lookback):
 def test_config1_through_cgraphg2o(tmp_path):
     assert _make().returncode == 0
     prefix = str(tmp_path / "cfg1")
-    r = subprocess.run([os.path.join(HOST, "run_g2o_graph"), "1000", "4", "0", prefix], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([os.path.join(REFBIN, "run_g2o_graph"), "1000", "4", "0", prefix], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     res = json.loads(r.stdout.strip().splitlines()[-1])
     before, after, poses, n_edges = _oracle_schedule(1000, 4)
@@ -129,7 +135,7 @@ def test_vo_failure_goes_through_fake_odo_node(tmp_path):
     fail = [100, 101, 500, 777]                                   # incl. two consecutive failures
     env = dict(os.environ, FGO_SYNTH_VO_FAIL=",".join(map(str, fail)))
     prefix = str(tmp_path / "fake")
-    r = subprocess.run([os.path.join(HOST, "run_g2o_graph"), "1000", "4", "0", prefix], capture_output=True, text=True, timeout=300, env=env)
+    r = subprocess.run([os.path.join(REFBIN, "run_g2o_graph"), "1000", "4", "0", prefix], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     res = json.loads(r.stdout.strip().splitlines()[-1])
     assert res["fake"] == len(fail) and res["nodes"] == 1000 and res["keyframes"] == 1000 - len(fail)
@@ -147,14 +153,14 @@ def test_vo_failure_goes_through_fake_odo_node(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(os.path.join(HOST, "_ref_test_g2o_graph")), reason="prebuilt reference driver not shipped")
+@pytest.mark.skipif(not os.path.exists(os.path.join(REFBIN, "_ref_test_g2o_graph")), reason="prebuilt reference driver not shipped")
 def test_reference_driver_with_vo_failures(tmp_path):
     """the same injection through the reference's unmodified driver binary (its own FAIL_KF -> fakeOdoNode branch)"""
     fail = [100, 101, 500, 777]
     env = dict(os.environ, FGO_SYNTH_POSES="1000", FGO_SYNTH_LOOKBACK="4", sr_start_frame="1", sr_end_frame="1001",
                gt_lookback_nodes="4", gt_optimize_step="250", gt_output_dir=str(tmp_path), sr_data_name="fake",
                FGO_SYNTH_VO_FAIL=",".join(map(str, fail)))
-    r = subprocess.run([os.path.join(HOST, "_ref_test_g2o_graph")], capture_output=True, text=True, timeout=600, env=env)
+    r = subprocess.run([os.path.join(REFBIN, "_ref_test_g2o_graph")], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stderr.splitlines() if "optimization error is" in l]
     assert len(lines) == 2
@@ -169,7 +175,7 @@ def test_online_schedule_with_periodic_optimisation():
     """optimizeGraph every 100 keyframes, as the online driver does (test_g2o_graph.cpp:78-84): the structure is
     rebuilt each time new vertices arrive; the end result must be a converged graph."""
     assert _make().returncode == 0
-    r = subprocess.run([os.path.join(HOST, "run_g2o_graph"), "600", "4", "100"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([os.path.join(REFBIN, "run_g2o_graph"), "600", "4", "100"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     res = json.loads(r.stdout.strip().splitlines()[-1])
     assert res["nodes"] == 600
@@ -178,12 +184,12 @@ def test_online_schedule_with_periodic_optimisation():
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(os.path.join(HOST, "_ref_test_g2o_graph")), reason="prebuilt reference driver not shipped")
+@pytest.mark.skipif(not os.path.exists(os.path.join(REFBIN, "_ref_test_g2o_graph")), reason="prebuilt reference driver not shipped")
 def test_reference_driver_runs_unchanged(tmp_path):
     """The reference's own driver binary (built in the container, shipped like a prebuilt .so) on config 1."""
     env = dict(os.environ, FGO_SYNTH_POSES="1000", FGO_SYNTH_LOOKBACK="4", sr_start_frame="1", sr_end_frame="1001",
                gt_lookback_nodes="4", gt_optimize_step="250", gt_output_dir=str(tmp_path), sr_data_name="cfg1")
-    r = subprocess.run([os.path.join(HOST, "_ref_test_g2o_graph")], capture_output=True, text=True, timeout=600, env=env)
+    r = subprocess.run([os.path.join(REFBIN, "_ref_test_g2o_graph")], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stderr.splitlines() if "optimization error is" in l]
     assert len(lines) == 2
@@ -215,9 +221,9 @@ GT_SYMS = ["CGraphGT::CGraphGT()", "CGraphGT::firstNode(CCameraNode*, bool)", "C
 def test_gtsam_side_library_builds_and_exports_surface():
     r = _make()
     assert r.returncode == 0, r.stderr[-2000:]
-    if not os.path.exists(os.path.join(HOST, "libgtsam_graph.so")):
+    if not os.path.exists(os.path.join(REFBIN, "libgtsam_graph.so")):
         pytest.skip("reference tree not present and no prebuilt wrapper library")
-    out = subprocess.run(["nm", "-DC", os.path.join(HOST, "libgtsam_graph.so")], capture_output=True, text=True).stdout
+    out = subprocess.run(["nm", "-DC", os.path.join(REFBIN, "libgtsam_graph.so")], capture_output=True, text=True).stdout
     for sym in GT_SYMS:
         assert sym in out, "missing symbol " + sym
 
@@ -336,7 +342,7 @@ def _errors(stderr):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(os.path.join(HOST, "_ref_test_vro_imu_graph")), reason="prebuilt reference driver not shipped")
+@pytest.mark.skipif(not os.path.exists(os.path.join(REFBIN, "_ref_test_vro_imu_graph")), reason="prebuilt reference driver not shipped")
 def test_reference_vio_driver_runs_unchanged(tmp_path):
     """gtsam/test_vro_imu_graph.cpp, compiled in place, on synthetic VRO + VN100 logs (BASELINE config 4's harness at a
     size the per-record ISAM2 flow finishes quickly): ISAM2 (fgo_isam2_update) after every record, error() and the
@@ -345,7 +351,7 @@ def test_reference_vio_driver_runs_unchanged(tmp_path):
     import graph_slam_amd as G
     n_kf = 80
     _make_logs(tmp_path, n_kf)
-    r = subprocess.run([os.path.join(HOST, "_ref_test_vro_imu_graph")], capture_output=True, text=True, timeout=900, env=_driver_env(tmp_path, n_kf, "vio"))
+    r = subprocess.run([os.path.join(REFBIN, "_ref_test_vro_imu_graph")], capture_output=True, text=True, timeout=900, env=_driver_env(tmp_path, n_kf, "vio"))
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     errs = _errors(r.stderr)
     assert len(errs) == 1, r.stderr[-1500:]
@@ -362,14 +368,14 @@ def test_reference_vio_driver_runs_unchanged(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(os.path.join(HOST, "_ref_test_ba_imu_graph")), reason="prebuilt reference driver not shipped")
+@pytest.mark.skipif(not os.path.exists(os.path.join(REFBIN, "_ref_test_ba_imu_graph")), reason="prebuilt reference driver not shipped")
 def test_reference_ba_imu_driver_runs_unchanged(tmp_path):
     """gtsam/test_ba_imu_graph.cpp (named by BASELINE.json's north star), compiled in place: same replay with use_imu,
     ISAM2 per record, then error(), optimizeGraphBatch() (fgo_optimize_gtsam) and error() again (:448-453)."""
     import graph_slam_amd as G
     n_kf = 60
     _make_logs(tmp_path, n_kf)
-    r = subprocess.run([os.path.join(HOST, "_ref_test_ba_imu_graph")], capture_output=True, text=True, timeout=900, env=_driver_env(tmp_path, n_kf, "ba"))
+    r = subprocess.run([os.path.join(REFBIN, "_ref_test_ba_imu_graph")], capture_output=True, text=True, timeout=900, env=_driver_env(tmp_path, n_kf, "ba"))
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     errs = _errors(r.stderr)
     assert len(errs) == 2, r.stderr[-1500:]
@@ -437,7 +443,7 @@ def _independent_error(vals, facs, calib=None, bps=None):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(os.path.join(HOST, "_ref_test_vro_imu_graph")), reason="prebuilt reference driver not shipped")
+@pytest.mark.skipif(not os.path.exists(os.path.join(REFBIN, "_ref_test_vro_imu_graph")), reason="prebuilt reference driver not shipped")
 def test_reference_vio_driver_plane_aided(tmp_path):
     """BASELINE config 4's third leg through the reference's OWN code (VERDICT r2 missing #2): plane_aided = 1.  VRO 'fails' on
     a few frames (void records), so gtsam/test_vro_imu_graph.cpp:202-314 runs its plane branch: CPlaneNode::extractPlanes (the
@@ -451,7 +457,7 @@ def test_reference_vio_driver_plane_aided(tmp_path):
     _make_logs(tmp_path, n_kf, vo_fail=fail)
     env = _driver_env(tmp_path, n_kf, "pvio")
     env.update(plane_aided="1", FGO_SYNTH_TRUTH=str(tmp_path / "truth.log"), FGO_GRAPH_DUMP=str(tmp_path / "graph_dump.txt"))
-    r = subprocess.run([os.path.join(HOST, "_ref_test_vro_imu_graph")], capture_output=True, text=True, timeout=900, env=env)
+    r = subprocess.run([os.path.join(REFBIN, "_ref_test_vro_imu_graph")], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
     errs = _errors(r.stderr)
     assert len(errs) == 1, r.stderr[-1500:]
@@ -483,13 +489,13 @@ def test_reference_vio_driver_plane_aided(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(os.path.join(HOST, "run_bundle_adjust")), reason="prebuilt harness not shipped")
+@pytest.mark.skipif(not os.path.exists(os.path.join(REFBIN, "run_bundle_adjust")), reason="prebuilt harness not shipped")
 def test_reference_bundle_adjust_two_view():
     """CGraphGT::bundleAdjust (gtsam/gtsam_graph.cpp:500-610, the reference's own code compiled in place): two-view BA with
     Cal3DS2 reprojection factors + point priors through LevenbergMarquardtOptimizer (fgo_optimize_gtsam), then
     Marginals::marginalCovariance of the second camera (fgo_marginal_cov) inverted into the edge's information matrix.
     The recovered relative pose must match the pose the synthetic features were generated with (noise: 0.3 px, 5-10 mm)."""
-    r = subprocess.run([os.path.join(HOST, "run_bundle_adjust"), "80", "3"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([os.path.join(REFBIN, "run_bundle_adjust"), "80", "3"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["max_abs_dt"] < 0.01 and d["max_abs_dR"] < 0.005, d
@@ -530,7 +536,7 @@ def test_g2o_file_load_optimise_save_roundtrip(tmp_path):
     assert "FIX 0" in out.read_text()
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(HOST, "run_imu_mems")), reason="prebuilt harness not shipped")
+@pytest.mark.skipif(not os.path.exists(os.path.join(REFBIN, "run_imu_mems")), reason="prebuilt harness not shipped")
 def test_reference_mems_imu_interface(tmp_path):
     """VERDICT r2 missing #7: the reference's CImuMEMS (gtsam/imu_MEMS.cpp, compiled in place) -- integer log `id1 gx gy gz ax ay az id2`,
     counts -> rad/s (Gi2V, through a float) and m/s^2 (Ai2V), synchronisation point where id1 restarts at 1, prior bias = mean of the
@@ -550,7 +556,7 @@ def test_reference_mems_imu_interface(tmp_path):
         rows.append((k + 1, g[0], g[1], g[2], a[0], a[1], a[2], k // 3 + 1))
     log = tmp_path / "mems.log"
     log.write_text("\n".join(" ".join(str(int(v)) for v in r) for r in rows))          # no trailing newline: the reader loops on eof()
-    r = subprocess.run([os.path.join(HOST, "run_imu_mems"), str(log), "200", "200", "260"], capture_output=True, text=True, timeout=60)
+    r = subprocess.run([os.path.join(REFBIN, "run_imu_mems"), str(log), "200", "200", "260"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stderr[-1500:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     raw = np.array(rows, dtype=np.int64)
@@ -577,7 +583,7 @@ def test_reference_mems_imu_interface(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(os.path.join(HOST, "run_ba_multiframe")), reason="prebuilt harness not shipped")
+@pytest.mark.skipif(not os.path.exists(os.path.join(REFBIN, "run_ba_multiframe")), reason="prebuilt harness not shipped")
 def test_reference_multiframe_ba_builder(tmp_path):
     """VERDICT r2 missing #3: the reference's OWN multi-frame bundle-adjustment builder, CGraphGT::addToGTSAM(CCameraNodeBA*,
     CCameraNodeBA*, matches, CamModel*) (gtsam/gtsam_graph.cpp:370-448, compiled in place; its call sites in the reference's
@@ -589,7 +595,7 @@ def test_reference_multiframe_ba_builder(tmp_path):
     is at the noise floor; the keyframe poses land on the truth."""
     pre = str(tmp_path / "dump")
     env = dict(os.environ, FGO_GRAPH_DUMP_PREFIX=pre, LD_LIBRARY_PATH=HOST + ":" + os.path.dirname(HOST) + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
-    r = subprocess.run([os.path.join(HOST, "run_ba_multiframe"), "60", "6000", "3", "5"], capture_output=True, text=True, timeout=900, env=env)
+    r = subprocess.run([os.path.join(REFBIN, "run_ba_multiframe"), "60", "6000", "3", "5"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["landmarks"] >= 1000 and d["keyframes"] == 60

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B or sweep of any tuning constant through the ONE override variable (csrc/fgo_internal.hpp tune()):
 #   tools/tune_sweep.sh out_tag "ride_win=18" "ride_win=22" "ride_win=26,ride_ops=400000" ...
-# runs bench.py once per setting (cfg 2, 20 timed iterations, median of 3 regions) and prints iterations/s and the phase times;
+# runs bench.py --full once per setting (cfg 2, 20 timed iterations, median of 3 regions) and prints iterations/s and the phase times;
 # BENCH_ARGS passes extra arguments (e.g. "--poses 1000000").  The keys are the lower-case names next to the constants:
 #   ordering   nd_leaf nd_bal_t nd_bal_w nd_starts nd_min_side dense_factor hub_deg
 #   schedule   leaf_blocks merge_multi chain_work acc_long acc2_min acc_v1 fwd_split dist_min_trees dist_max_share
@@ -11,12 +11,13 @@
 #   isam2      isam_lookahead isam_masked isam_ranges (0: the plain forms, for A/B runs and the equivalence test)
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 TAG=$1; shift
-mkdir -p gpurun_out/$TAG
+OUT=${SWEEP_OUT:-sweep_out}/$TAG       # SWEEP_OUT: where the per-setting lines and the table go
+mkdir -p "$OUT"
 for cfg in "$@"; do
-  FGO_TUNE="$cfg" timeout 600 python bench.py --steps 20 --warmup 5 --cpu-iters 0 --repeats 3 ${BENCH_ARGS:-} > gpurun_out/$TAG/b.json 2> gpurun_out/$TAG/b.err
-  python - "$cfg" gpurun_out/$TAG/b.json <<'PY'
+  FGO_TUNE="$cfg" timeout 600 python bench.py --full --steps 20 --warmup 5 --cpu-iters 0 --repeats 3 ${BENCH_ARGS:-} > "$OUT/b.json" 2> "$OUT/b.err"
+  python - "$cfg" "$OUT/b.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 print("%-40s %8.2f it/s   linearise / sweep / backward ms: %s   levels %d  nnzL %d  ops %d  t_sym %.3f" % (sys.argv[1] or "(defaults)", d["value"], " / ".join("%.3f" % v for v in d["roofline"]["phases_ms"].values()), d["structure"]["levels"], d["structure"]["nnz_L_blocks"], d["structure"]["update_ops"], d["t_symbolic_s"]))
 PY
-done | tee gpurun_out/$TAG/sweep.txt
+done | tee "$OUT/sweep.txt"
