@@ -95,6 +95,10 @@ def _load():
     lib.fgo_set_growth.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.fgo_isam2_set_wildfire.argtypes = [C.c_void_p, C.c_double]
     lib.fgo_marginal_cov_many.argtypes = [C.c_void_p, C.c_int64, i64p, dp]
+    lib.fgo_marginal_cov_all.restype = C.c_int64
+    lib.fgo_marginal_cov_all.argtypes = [C.c_void_p, C.c_int64, i64p, dp]
+    lib.fgo_marginal_cov_pairs.argtypes = [C.c_void_p, C.c_int64, i64p, i64p, dp]
+    lib.fgo_debug_selinv_stats.argtypes = [C.c_void_p, dp]
     lib.fgo_dist_unique_id.argtypes = [C.c_void_p]
     lib.fgo_dist_init_rccl.argtypes = [C.c_void_p, C.c_void_p]
     lib.fgo_debug_partition.argtypes = [C.c_int, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
@@ -391,6 +395,42 @@ class Graph:
         out = np.zeros((len(ids), 6, 6))
         self._chk(lib.fgo_marginal_cov_many(self._h, len(ids), _i64p(ids), _dp(out)))
         return out
+
+    def marginal_cov_all(self):
+        """(ids, cov[n, 6, 6]): the marginal covariance of every free variable from one selected inversion"""
+        n = self._chk(lib.fgo_marginal_cov_all(self._h, 0, None, None))
+        ids = np.zeros(n, np.int64)
+        out = np.zeros((n, 6, 6))
+        self._chk(lib.fgo_marginal_cov_all(self._h, n, _i64p(ids), _dp(out)))
+        return ids, out
+
+    def marginal_cov_pairs(self, a, b):
+        """cov[n, 6, 6]: Cov(x_a[k], x_b[k]), rows in a's tangent, columns in b's"""
+        a = np.ascontiguousarray(a, np.int64); b = np.ascontiguousarray(b, np.int64)
+        assert a.shape == b.shape and a.ndim == 1
+        out = np.zeros((len(a), 6, 6))
+        self._chk(lib.fgo_marginal_cov_pairs(self._h, len(a), _i64p(a), _i64p(b), _dp(out)))
+        return out
+
+    def joint_marginal_cov(self, ids):
+        """dense (6n x 6n) joint covariance of the variables `ids` (GTSAM Marginals::jointMarginalCovariance)"""
+        ids = np.ascontiguousarray(ids, np.int64)
+        n = len(ids)
+        ia, ib = np.triu_indices(n)
+        blk = self.marginal_cov_pairs(ids[ia], ids[ib])
+        J = np.zeros((6 * n, 6 * n))
+        for k in range(len(ia)):
+            i, j = ia[k], ib[k]
+            J[6 * i:6 * i + 6, 6 * j:6 * j + 6] = blk[k]
+            J[6 * j:6 * j + 6, 6 * i:6 * i + 6] = blk[k].T
+        return J
+
+    def selinv_stats(self):
+        """timings of the last selected inversion (fgo_debug_selinv_stats)"""
+        out = np.zeros(7)
+        self._chk(lib.fgo_debug_selinv_stats(self._h, _dp(out)))
+        return dict(t_lists_s=out[0], list_bytes=int(out[1]), ms_factor=out[2], ms_prep=out[3], ms_sweep=out[4], entries=int(out[5]),
+                    fallback_pairs=int(out[6]))
 
     def add_plane(self, pid, abcd):
         a = np.ascontiguousarray(abcd, np.float64)

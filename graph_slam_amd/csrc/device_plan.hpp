@@ -314,4 +314,20 @@ void launch_isam2_relin(const DevPlan &P, double *theta, double *delta, double t
 void launch_isam2_estimate(const DevPlan &P, const double *theta, const double *x, double *delta, double *est, hipStream_t s,
                            unsigned char *moved_next = nullptr, double thr_next = 0);
 
+// ---- selected inversion (kernels_sinv.hip): H^-1 on the block pattern of the resident undamped factor.  The tables are
+// built on the first marginal request (fgo_selinv.cpp), never in the structure phase.
+struct SinvPlan {
+  int nb;
+  const int64_t *colptr;        // [nb + 1] block-CSC of L (diagonal first, ascending rows)
+  const int *task_ptr, *task_cols;
+  const int64_t *sptr;          // [nb + 1] -> sidx: column j's pair table, m (m + 1) / 2 entries (m off-diagonal blocks)
+  const int *sidx;              // entry p (p + 1) / 2 + q, q <= p: block of L (and of Sigma) at (r_p, r_q)
+  const double *U;              // [nnzL][36]: C_j = L_jj^-T L_jj^-1 at the diagonal slot, U_kj = L_kj L_jj^-1 at the others
+  double *Sig;                  // [nnzL][36]: Sigma = H^-1 on the pattern of L
+};
+void launch_sinv_prep(const SinvPlan &Q, const double *Lv, double *U, hipStream_t s);
+void launch_sinv_sweep(const SinvPlan &Q, const HostSchedule &H, hipStream_t s);      // reverse levels, one workgroup per task
+void launch_sinv_gather(const int64_t *enc, int64_t n, const double *Sig, double *out, hipStream_t s);   // enc: block << 1 | transpose
+void launch_sinv_rows(const int *cols, int64_t n, const double *x, double *out, hipStream_t s);          // out[i] = x rows of column cols[i]
+
 }  // namespace fgo

@@ -40,6 +40,7 @@ int upload_poses(fgo_ctx *c) {
   c->dev_poses_newer = false;
   c->lin_valid = false;
   c->cov_factor_valid = false;
+  c->sinv.valid = false;
   return FGO_OK;
 }
 

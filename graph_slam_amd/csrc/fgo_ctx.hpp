@@ -138,6 +138,22 @@ struct fgo_ctx {
   int cur = 0;                      // which of the double buffers holds the current estimate
   bool cov_factor_valid = false;    // d_L holds the undamped factor of the current linearisation (marginal covariances)
   std::vector<int> h_pose_col;      // host copy of pose_col (marginal covariances)
+  // selected inversion (fgo_selinv.cpp, kernels_sinv.hip): pair tables built on the first request after a structure build and
+  // released with the structure; Sigma = H^-1 on the pattern of the resident undamped factor (valid implies cov_factor_valid).
+  // U is scratch of one inversion (freed after the sweep); Sigma (nnzL x 288 B) stays resident until the structure is rebuilt
+  struct SelInv {
+    bool lists = false, valid = false;
+    fgo::DevBuf<int64_t> d_sptr, d_enc;
+    fgo::DevBuf<int> d_sidx;
+    fgo::DevBuf<double> d_U, d_Sig, d_out;
+    double t_build = 0, ms_factor = 0, ms_prep = 0, ms_sweep = 0;   // host seconds of the tables; device ms of the last factor / prep / sweep
+    int64_t n_entries = 0, list_bytes = 0;
+    int64_t n_fallback = 0;         // pairs of the last fgo_marginal_cov_pairs call served by column solves (off the pattern of L)
+    void release() {
+      lists = valid = false;
+      d_sptr.release(); d_enc.release(); d_sidx.release(); d_U.release(); d_Sig.release(); d_out.release();
+    }
+  } sinv;
   // ---- ISAM2 state (fgo_isam2_update): linearisation point and linear solution per variable, variable order
   fgo::DevBuf<double> d_theta, d_delta;  // 8 / 6 doubles per variable
   // partial re-factorisation: d_L / d_y hold the factor and forward solution of the previous ISAM2 step (isam_L_valid);

@@ -118,6 +118,7 @@ int fgo_debug_read_reduced(fgo_ctx *c, double lambda, double *H_dense, double *b
   HIPCHK(c, hipMemcpyAsync(c->d_scal.p + 3, c->h_scal + 3, sizeof(double), hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemsetAsync(c->d_fail.p, 0, sizeof(int), s));
   c->cov_factor_valid = false;
+  c->sinv.valid = false;
   launch_ba_reduce(c->plan, c->ba.d_W[c->cur].p, c->ba.d_Hpp[c->cur].p, c->ba.d_bp[c->cur].p, c->d_H[c->cur].p, c->d_b[c->cur].p,
                    c->ba.d_Hred.p, c->ba.d_bred.p, c->d_scal.p + 3, c->d_fail.p, s);
   HIPCHK(c, hipStreamSynchronize(s));
@@ -154,7 +155,7 @@ static int marginal_blocks(fgo_ctx *c, int64_t n, const int64_t *ids, double *co
     if (lm) { ba_off(c); rc = ensure_ready(c); if (rc) return rc; }
   }
   hipStream_t s = c->stream;
-  if (!c->lin_valid) { rc = linearize_current(c, false); if (rc) return rc; c->cov_factor_valid = false; }
+  if (!c->lin_valid) { rc = linearize_current(c, false); if (rc) return rc; c->cov_factor_valid = false; c->sinv.valid = false; }
   if (!c->cov_factor_valid) {
     c->h_scal[3] = 0.0;
     HIPCHK(c, hipMemcpyAsync(c->d_scal.p + 3, c->h_scal + 3, sizeof(double), hipMemcpyHostToDevice, s));
@@ -216,6 +217,7 @@ int fgo_solve_step(fgo_ctx *c, double lambda, double *delta_out) try {
   HIPCHK(c, hipMemcpyAsync(c->d_scal.p + 3, c->h_scal + 3, sizeof(double), hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemsetAsync(c->d_fail.p, 0, sizeof(int), s));
   c->cov_factor_valid = false;
+  c->sinv.valid = false;
   c->isam_L_valid = false;
   launch_factor(c->plan, c->sched, c->d_H[c->cur].p, c->d_L.p, c->d_scal.p + 3, c->d_fail.p, s);
   launch_solve(c->plan, c->sched, c->d_L.p, c->d_b[c->cur].p, c->d_x.p, s);
@@ -240,6 +242,7 @@ int fgo_bench_phase(fgo_ctx *c, int phase, int reps, double *ms_out) try {
   if (!c->lin_valid) { rc = linearize_current(c, true); if (rc) return rc; }
   hipStream_t s = c->stream;
   c->cov_factor_valid = false;
+  c->sinv.valid = false;
   c->isam_L_valid = false;
   if (phase >= 1) {   // make sure lambda and (for the solve) a valid factor are in place
     c->h_scal[3] = 1e-5 * std::max(1.0, c->h_scal[2]);

@@ -161,6 +161,7 @@ int fgo_isam2_update(fgo_ctx *c, double relin_threshold, fgo_stats *stats) try {
     HIPCHK(c, hipEventRecord(c->ev[1], s));
   }
   c->cov_factor_valid = false;
+  c->sinv.valid = false;
   c->isam_L_valid = false;                              // (until this step has gone through)
   if (plan.task_dirty) launch_mix_rhs(plan, c->d_b[w].p, c->d_y.p, c->d_x.p, c->d_col_dirty.p, s);
   PartialSweep ps{};

@@ -62,6 +62,7 @@ void enqueue_trial(fgo_ctx *c, int cur, bool with_events) {
 
 int run_trial(fgo_ctx *c, double lambda, double *chi_cand, double *scale, int *failed, fgo_stats *st) {
   c->cov_factor_valid = false;
+  c->sinv.valid = false;
   c->isam_L_valid = false;
   if (c->shard_world > 1) return run_trial_dist(c, lambda, chi_cand, scale, failed, st);
   hipStream_t s = c->stream;
@@ -115,6 +116,7 @@ int run_trial(fgo_ctx *c, double lambda, double *chi_cand, double *scale, int *f
 int linearize_current(fgo_ctx *c, bool want_maxdiag) {
   hipStream_t s = c->stream;
   c->cov_factor_valid = false;
+  c->sinv.valid = false;
   ctx_linearize(c, c->cur, c->d_scal.p + 0);
   { const int rc = dist_sum_scalars(c, 0, 1); if (rc) return rc; }                    // chi2: partial sums over the ranks' factors
   if (c->shard_world > 1) {                                                           // complete the gradient of the top

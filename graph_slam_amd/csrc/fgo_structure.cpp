@@ -1434,6 +1434,7 @@ struct StructureBuild {
   c->built_N = N;
   c->cur = 0;
   c->cov_factor_valid = false;
+  c->sinv.release();                                  // the selected inversion's tables belong to the old structure
   c->h_pose_col.clear();
   c->structure_dirty = false;
   c->host_poses_newer = true;
@@ -1731,6 +1732,7 @@ int refresh_factors(fgo_ctx *c) {
   c->structure_dirty = false;
   c->lin_valid = false;
   c->cov_factor_valid = false;
+  c->sinv.valid = false;
   fgo_stats &st = c->last;
   st.structure_rebuilt = 0;
   st.t_symbolic = now_s() - t0;                                 // host time of the in-place extension

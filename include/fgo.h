@@ -235,6 +235,21 @@ int fgo_marginal_cov(fgo_ctx *ctx, int64_t id, double *cov36);
  * :1357 + the commented-out association test :1413-1414): cov36 = n x 36 doubles.  The undamped factor stays resident in
  * HBM until the estimate or the structure changes, so consecutive calls do not re-factor either. */
 int fgo_marginal_cov_many(fgo_ctx *ctx, int64_t n, const int64_t *ids, double *cov36);
+/* SparseOptimizer::computeMarginals / Marginals for the whole map: the H^-1 diagonal blocks of EVERY free variable from one
+ * selected inversion of the resident undamped factor (H^-1 on the block pattern of L, one reverse sweep over the factor's
+ * level schedule).  Same semantics as fgo_marginal_cov; ids_out (n) / cov36_out (n x 36) in the order the variables were
+ * added.  Returns the count n (ids_out / cov36_out may be NULL with cap 0 to query it), FGO_EINVAL if cap < n.  On a
+ * bundle-adjustment graph the landmarks are included (the context switches to the generic form, like a landmark's
+ * fgo_marginal_cov). */
+int64_t fgo_marginal_cov_all(fgo_ctx *ctx, int64_t cap, int64_t *ids_out, double *cov36_out);
+/* Cov(x_a, x_b) 6x6 row-major (rows: a's tangent, cols: b's); a == b is the marginal.  Pairs on the factor's pattern
+ * (every pair sharing a factor is) come from the selected inverse; other pairs by column solves, grouped by b.
+ * Marginals::jointMarginalCovariance is assembled from these blocks. */
+int fgo_marginal_cov_pairs(fgo_ctx *ctx, int64_t n, const int64_t *id_a, const int64_t *id_b, double *cov36);
+/* timings of the last selected inversion: [0] host seconds of the pair tables, [1] their bytes, [2] device ms of the undamped
+ * factorisation, [3] of the prep kernel, [4] of the reverse sweep, [5] pair-table entries, [6] pairs of the last
+ * fgo_marginal_cov_pairs call that were off the factor's pattern (served by column solves) */
+int fgo_debug_selinv_stats(const fgo_ctx *ctx, double out[7]);
 
 /* ---- solve: ONE SparseOptimizer::optimize(max_iters) call as issued by
  *      CGraphG2O::optimizeGraph (g2o/g2o_graph.cpp:246-249).  Returns the number of LM iterations
