@@ -315,7 +315,7 @@ void launch_isam2_estimate(const DevPlan &P, const double *theta, const double *
                            unsigned char *moved_next = nullptr, double thr_next = 0);
 
 // ---- selected inversion (kernels_sinv.hip): H^-1 on the block pattern of the resident undamped factor.  The tables are
-// built on the first marginal request (fgo_selinv.cpp), never in the structure phase.
+// built on the first marginal request that needs them (fgo_marginals.cpp), never in the structure phase.
 struct SinvPlan {
   int nb;
   const int64_t *colptr;        // [nb + 1] block-CSC of L (diagonal first, ascending rows)

@@ -39,8 +39,7 @@ int upload_poses(fgo_ctx *c) {
   c->host_poses_newer = false;
   c->dev_poses_newer = false;
   c->lin_valid = false;
-  c->cov_factor_valid = false;
-  c->sinv.valid = false;
+  drop_undamped(c);
   return FGO_OK;
 }
 
@@ -190,6 +189,7 @@ int fgo_set_fixed(fgo_ctx *c, int64_t id, int fixed) try {
     c->inc.valid = false;                 // (not something the in-place extension of the incremental mode can express)
     c->host_poses_newer = true;
     c->lin_valid = false;
+    drop_undamped(c);
   }
   return FGO_OK;
 } FGO_CATCH_INT(c)

@@ -51,6 +51,14 @@ struct DevBuf {
   void swap(DevBuf &o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(cap, o.cap); }
 };
 
+// What the resident factor d_L holds (fgo_ctx::L_holds; only claim_L / record_L / drop_undamped / drop_isam_step assign it):
+//   scratch         nothing to reuse: an LM trial's damped factor, fgo_solve_step / fgo_bench_phase, a failed factorisation
+//   undamped        the undamped factor of the current linearisation (marginal covariances, fgo_marginals.cpp)
+//   undamped_sigma  the same, and fgo_ctx::sinv holds Sigma = H^-1 on its pattern
+//   isam_step       the factor of the previous ISAM2 step, d_y its forward solution: the next update may re-factor only the
+//                   tasks on the paths from the affected variables to the roots
+enum class LHolds { scratch, undamped, undamped_sigma, isam_step };
+
 }  // namespace fgo
 
 struct fgo_ctx {
@@ -136,13 +144,13 @@ struct fgo_ctx {
   fgo::DevBuf<int> d_imu_ids, d_imu_slot;
   fgo::DevBuf<double> d_prior_minv, d_prior_info;
   int cur = 0;                      // which of the double buffers holds the current estimate
-  bool cov_factor_valid = false;    // d_L holds the undamped factor of the current linearisation (marginal covariances)
+  fgo::LHolds L_holds = fgo::LHolds::scratch;   // what d_L holds (fgo::LHolds)
   std::vector<int> h_pose_col;      // host copy of pose_col (marginal covariances)
-  // selected inversion (fgo_selinv.cpp, kernels_sinv.hip): pair tables built on the first request after a structure build and
-  // released with the structure; Sigma = H^-1 on the pattern of the resident undamped factor (valid implies cov_factor_valid).
+  // selected inversion (fgo_marginals.cpp, kernels_sinv.hip): pair tables built on the first request after a structure build and
+  // released with the structure; Sigma = H^-1 on the pattern of the resident undamped factor (current while L_holds says so).
   // U is scratch of one inversion (freed after the sweep); Sigma (nnzL x 288 B) stays resident until the structure is rebuilt
   struct SelInv {
-    bool lists = false, valid = false;
+    bool lists = false;
     fgo::DevBuf<int64_t> d_sptr, d_enc;
     fgo::DevBuf<int> d_sidx;
     fgo::DevBuf<double> d_U, d_Sig, d_out;
@@ -150,15 +158,14 @@ struct fgo_ctx {
     int64_t n_entries = 0, list_bytes = 0;
     int64_t n_fallback = 0;         // pairs of the last fgo_marginal_cov_pairs call served by column solves (off the pattern of L)
     void release() {
-      lists = valid = false;
+      lists = false;
       d_sptr.release(); d_enc.release(); d_sidx.release(); d_U.release(); d_Sig.release(); d_out.release();
     }
   } sinv;
   // ---- ISAM2 state (fgo_isam2_update): linearisation point and linear solution per variable, variable order
   fgo::DevBuf<double> d_theta, d_delta;  // 8 / 6 doubles per variable
-  // partial re-factorisation: d_L / d_y hold the factor and forward solution of the previous ISAM2 step (isam_L_valid);
-  // an update re-runs only the tasks on the paths from the affected variables to the roots (task_dirty)
-  bool isam_L_valid = false;
+  // partial re-factorisation (L_holds == isam_step): an update re-runs only the tasks on the paths from the affected variables
+  // to the roots (task_dirty)
   int64_t isam_E_seen = 0, isam_NI_seen = 0, isam_NP_seen = 0;   // factors the previous step already knew
   std::vector<int> col_task;        // [nb] task of every column (host)
   fgo::DevBuf<double> d_y;
@@ -294,6 +301,12 @@ void ctx_linearize(fgo_ctx *c, int buf, double *scalar_out);
 void ctx_factor(fgo_ctx *c, int buf, bool with_rhs);          // with_rhs: forward solve fused into the sweep (x <- y)
 void ctx_solve(fgo_ctx *c, int buf, bool fwd_done);           // backward sweep (or both), then the landmarks' back-substitution
 void ba_off(fgo_ctx *c);                                      // this context gives up the eliminated form (next build: generic)
+hipError_t stage_lambda(fgo_ctx *c, double lambda);           // lambda into d_scal[3], failure flag zeroed: before a factorisation outside the LM trial
+// what d_L holds (fgo::LHolds); nothing else assigns fgo_ctx::L_holds
+void claim_L(fgo_ctx *c);                                     // d_L is about to be written: scratch until record_L
+void record_L(fgo_ctx *c, LHolds what);                       // the writer is done: d_L holds `what`
+void drop_undamped(fgo_ctx *c);                               // the linearisation changed: an undamped factor (and its Sigma) is stale
+void drop_isam_step(fgo_ctx *c);                              // the ISAM2 state was reset: its previous step's factor is no longer continued
 int linearize_current(fgo_ctx *c, bool want_maxdiag);
 
 }  // namespace fgo

@@ -1,4 +1,4 @@
-// Read-back, marginal covariances, stand-alone solve and the bench hooks of libfgo.
+// Read-back, stand-alone solve and the bench hooks of libfgo.
 #include "fgo_ctx.hpp"
 
 using namespace fgo;
@@ -17,6 +17,7 @@ int fgo_debug_read_system(fgo_ctx *c, double *H, double *b, double *chi2) try {
   if (c->gtsam_mode) launch_linearize_gtsam(c->plan, c->d_poses[c->cur].p, c->d_H[c->cur].p, c->d_b[c->cur].p, c->d_scal.p + 0, s);
   else launch_linearize(c->plan, c->d_poses[c->cur].p, c->d_H[c->cur].p, c->d_b[c->cur].p, c->d_scal.p + 0, s);
   c->lin_valid = false;
+  drop_undamped(c);
   if (H) HIPCHK(c, hipMemcpyAsync(H, c->d_H[c->cur].p, sizeof(double) * 36 * (size_t)c->plan.n_hblocks, hipMemcpyDeviceToHost, s));
   if (b) HIPCHK(c, hipMemcpyAsync(b, c->d_b[c->cur].p, sizeof(double) * 6 * (size_t)c->plan.nb, hipMemcpyDeviceToHost, s));
   if (chi2) HIPCHK(c, hipMemcpyAsync(chi2, c->d_scal.p, sizeof(double), hipMemcpyDeviceToHost, s));
@@ -114,94 +115,12 @@ int fgo_debug_read_reduced(fgo_ctx *c, double lambda, double *H_dense, double *b
   if (n_out) *n_out = (int64_t)c->plan.nb - c->n_phantom;
   if (!H_dense && !b_dense) return FGO_OK;
   hipStream_t s = c->stream;
-  c->h_scal[3] = lambda;
-  HIPCHK(c, hipMemcpyAsync(c->d_scal.p + 3, c->h_scal + 3, sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemsetAsync(c->d_fail.p, 0, sizeof(int), s));
-  c->cov_factor_valid = false;
-  c->sinv.valid = false;
+  HIPCHK(c, stage_lambda(c, lambda));
   launch_ba_reduce(c->plan, c->ba.d_W[c->cur].p, c->ba.d_Hpp[c->cur].p, c->ba.d_bp[c->cur].p, c->d_H[c->cur].p, c->d_b[c->cur].p,
                    c->ba.d_Hred.p, c->ba.d_bred.p, c->d_scal.p + 3, c->d_fail.p, s);
   HIPCHK(c, hipStreamSynchronize(s));
   HIPCHK(c, hipGetLastError());
   return dense_from_blocks(c, c->ba.d_Hred.p, c->ba.d_bred.p, H_dense, b_dense);
-} FGO_CATCH_INT(c)
-
-// Marginals(graph, values, CHOLESKY).marginalCovariance(key): the (id, id) block of (J' Omega J)^-1 at the current
-// linearisation (gtsam/gtsam_graph.cpp:598-601).  The reference pays a full batch factorisation per call (and builds
-// one it never uses at :1357); here the factor stays resident in HBM: one undamped factorisation per linearisation
-// point, then 6 pairs of triangular solves per requested block.
-// one undamped factorisation of the current linearisation, kept resident (c->cov_factor_valid) until the estimate or
-// the structure changes; then the requested diagonal blocks of H^-1: 6 pairs of triangular solves per block
-static int marginal_blocks(fgo_ctx *c, int64_t n, const int64_t *ids, double *cov36) {
-  (void)hipSetDevice(c->cfg.device);
-  if (c->shard_world > 1) return fail(c, FGO_ESTATE, "marginal covariances: not available in distributed mode");
-  int rc = ensure_ready(c);
-  if (rc) return rc;
-  std::vector<int> idx((size_t)n);
-  for (int64_t q = 0; q < n; ++q) {
-    auto it = c->id2idx.find(ids[q]);
-    if (it == c->id2idx.end()) return fail(c, FGO_EINVAL, "unknown variable id");
-    if (c->fixed[it->second]) return fail(c, FGO_EINVAL, "a fixed vertex has no marginal covariance");
-    idx[q] = it->second;
-  }
-  if (c->ba.on) {
-    // cameras: the inverse of the reduced system IS their marginal; an eliminated landmark has no column -> generic form
-    if (c->h_pose_col.size() != c->ids.size()) {
-      c->h_pose_col.resize(c->ids.size());
-      HIPCHK(c, hipMemcpy(c->h_pose_col.data(), c->d_pose_col.p, sizeof(int) * c->h_pose_col.size(), hipMemcpyDeviceToHost));
-    }
-    bool lm = false;
-    for (int64_t q = 0; q < n; ++q) lm = lm || c->h_pose_col[idx[q]] >= c->plan.nb;
-    if (lm) { ba_off(c); rc = ensure_ready(c); if (rc) return rc; }
-  }
-  hipStream_t s = c->stream;
-  if (!c->lin_valid) { rc = linearize_current(c, false); if (rc) return rc; c->cov_factor_valid = false; c->sinv.valid = false; }
-  if (!c->cov_factor_valid) {
-    c->h_scal[3] = 0.0;
-    HIPCHK(c, hipMemcpyAsync(c->d_scal.p + 3, c->h_scal + 3, sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemsetAsync(c->d_fail.p, 0, sizeof(int), s));
-    c->isam_L_valid = false;
-    ctx_factor(c, c->cur, false);
-    HIPCHK(c, hipMemcpyAsync(c->h_fail, c->d_fail.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (*c->h_fail) return fail(c, FGO_ENUM, "information matrix not positive definite (gauge freedom left?)");
-    c->cov_factor_valid = true;
-  }
-  if (c->h_pose_col.size() != c->ids.size()) {           // permuted column of every variable (host copy, once per structure)
-    c->h_pose_col.resize(c->ids.size());
-    HIPCHK(c, hipMemcpy(c->h_pose_col.data(), c->d_pose_col.p, sizeof(int) * c->h_pose_col.size(), hipMemcpyDeviceToHost));
-  }
-  const int nb = c->plan.nb;
-  DevBuf<double> rhs;
-  HIPCHK(c, rhs.alloc((size_t)nb * 6));
-  for (int64_t q = 0; q < n; ++q) {
-    const int col = c->h_pose_col[idx[q]];
-    double blk[6];
-    for (int k = 0; k < 6; ++k) {
-      HIPCHK(c, hipMemsetAsync(rhs.p, 0, sizeof(double) * (size_t)nb * 6, s));
-      const double one = 1.0;
-      HIPCHK(c, hipMemcpyAsync(rhs.p + 6 * (size_t)col + k, &one, sizeof(double), hipMemcpyHostToDevice, s));
-      launch_solve(c->plan, c->sched, c->d_L.p, rhs.p, c->d_x.p, s);
-      HIPCHK(c, hipMemcpyAsync(blk, c->d_x.p + 6 * (size_t)col, sizeof(blk), hipMemcpyDeviceToHost, s));
-      HIPCHK(c, hipStreamSynchronize(s));
-      for (int r = 0; r < 6; ++r) cov36[36 * q + r * 6 + k] = blk[r];
-    }
-  }
-  HIPCHK(c, hipGetLastError());
-  return FGO_OK;
-}
-
-// Marginals(graph, values, CHOLESKY).marginalCovariance(key): the (id, id) block of (J' Omega J)^-1 at the current
-// linearisation (gtsam/gtsam_graph.cpp:598-601).  The reference pays a full batch factorisation per Marginals object (and
-// builds one it never uses at :1357); here the factor stays resident in HBM across calls.
-int fgo_marginal_cov(fgo_ctx *c, int64_t id, double *cov36) try {
-  if (!c || !cov36) return FGO_EINVAL;
-  return marginal_blocks(c, 1, &id, cov36);
-} FGO_CATCH_INT(c)
-
-int fgo_marginal_cov_many(fgo_ctx *c, int64_t n, const int64_t *ids, double *cov36) try {
-  if (!c || n < 0 || (n > 0 && (!ids || !cov36))) return FGO_EINVAL;
-  return n == 0 ? FGO_OK : marginal_blocks(c, n, ids, cov36);
 } FGO_CATCH_INT(c)
 
 int fgo_solve_step(fgo_ctx *c, double lambda, double *delta_out) try {
@@ -213,12 +132,8 @@ int fgo_solve_step(fgo_ctx *c, double lambda, double *delta_out) try {
   if (rc) return rc;
   if (!c->lin_valid) { rc = linearize_current(c, false); if (rc) return rc; }
   hipStream_t s = c->stream;
-  c->h_scal[3] = lambda;
-  HIPCHK(c, hipMemcpyAsync(c->d_scal.p + 3, c->h_scal + 3, sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemsetAsync(c->d_fail.p, 0, sizeof(int), s));
-  c->cov_factor_valid = false;
-  c->sinv.valid = false;
-  c->isam_L_valid = false;
+  claim_L(c);
+  HIPCHK(c, stage_lambda(c, lambda));
   launch_factor(c->plan, c->sched, c->d_H[c->cur].p, c->d_L.p, c->d_scal.p + 3, c->d_fail.p, s);
   launch_solve(c->plan, c->sched, c->d_L.p, c->d_b[c->cur].p, c->d_x.p, s);
   const int nb = c->plan.nb;
@@ -241,12 +156,9 @@ int fgo_bench_phase(fgo_ctx *c, int phase, int reps, double *ms_out) try {
   if (rc) return rc;
   if (!c->lin_valid) { rc = linearize_current(c, true); if (rc) return rc; }
   hipStream_t s = c->stream;
-  c->cov_factor_valid = false;
-  c->sinv.valid = false;
-  c->isam_L_valid = false;
+  claim_L(c);
   if (phase >= 1) {   // make sure lambda and (for the solve) a valid factor are in place
-    c->h_scal[3] = 1e-5 * std::max(1.0, c->h_scal[2]);
-    HIPCHK(c, hipMemcpyAsync(c->d_scal.p + 3, c->h_scal + 3, sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(c, stage_lambda(c, 1e-5 * std::max(1.0, c->h_scal[2])));
     ctx_factor(c, c->cur, true);
   }
   HIPCHK(c, hipStreamSynchronize(s));

@@ -58,9 +58,7 @@ int fgo_isam2_update(fgo_ctx *c, double relin_threshold, fgo_stats *stats) try {
   st.ms_factor = st.ms_solve = st.ms_update = st.ms_linearize = 0; st.reserved[0] = 0;
   double *scal = c->d_scal.p;
   const int w = c->cur ^ 1;                             // H / b of the side buffers: the current ones stay valid for the values
-  c->h_scal[3] = 0.0;                                   // Gauss-Newton: no damping (ISAM2GaussNewtonParams)
-  HIPCHK(c, hipMemcpyAsync(scal + 3, c->h_scal + 3, sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemsetAsync(c->d_fail.p, 0, sizeof(int), s));
+  HIPCHK(c, stage_lambda(c, 0.0));                      // Gauss-Newton: no damping (ISAM2GaussNewtonParams)
   HIPCHK(c, hipEventRecord(c->ev[0], s));
   // ---- partial re-factorisation.  ISAM2 re-eliminates only the cliques on the paths from the affected variables to the
   // root of the Bayes tree; here: only the TASKS of the elimination tree on those paths are run again (k_* kernels skip
@@ -76,7 +74,7 @@ int fgo_isam2_update(fgo_ctx *c, double relin_threshold, fgo_stats *stats) try {
   const fgo_ctx::Incr &I = c->inc;
   const int64_t E = (int64_t)c->ei.size(), NI = (int64_t)c->imu_payload.size(), NPr = (int64_t)c->prior_v.size();
   const bool have_tables = !c->col_task.empty() && I.valid && c->d_y.p != nullptr;
-  const bool partial = partial_on && have_tables && c->isam_L_valid;
+  const bool partial = partial_on && have_tables && c->L_holds == LHolds::isam_step;
   // which variables k_isam2_relin moves is known since the END of the previous update (same delta, same test: k_isam2_estimate)
   // unless the threshold or the structure changed in between -- then the flags come back here, at the price of a synchronisation
   static const bool look_on = tune("isam_lookahead", 1) != 0;
@@ -160,9 +158,7 @@ int fgo_isam2_update(fgo_ctx *c, double relin_threshold, fgo_stats *stats) try {
     else launch_linearize_gtsam(c->plan, c->d_theta.p, c->d_H[w].p, c->d_b[w].p, scal + 4, s);
     HIPCHK(c, hipEventRecord(c->ev[1], s));
   }
-  c->cov_factor_valid = false;
-  c->sinv.valid = false;
-  c->isam_L_valid = false;                              // (until this step has gone through)
+  claim_L(c);
   if (plan.task_dirty) launch_mix_rhs(plan, c->d_b[w].p, c->d_y.p, c->d_x.p, c->d_col_dirty.p, s);
   PartialSweep ps{};
   const bool ranged = plan.task_dirty && c->tk_ok && !c->task_level.empty();
@@ -206,7 +202,7 @@ int fgo_isam2_update(fgo_ctx *c, double relin_threshold, fgo_stats *stats) try {
     c->last = st;
     return fail(c, FGO_ENUM, "ISAM2 update: linear system not positive definite (IndeterminantLinearSystemException)");
   }
-  c->isam_L_valid = have_tables;
+  if (have_tables) record_L(c, LHolds::isam_step);
   c->isam_H_valid = maskable;
   c->wild_valid = wild_possible;
   c->isam_E_seen = E; c->isam_NI_seen = NI; c->isam_NP_seen = NPr;
@@ -273,7 +269,7 @@ int fgo_isam2_reset(fgo_ctx *c) try {
   c->d_theta.release(); c->d_delta.release();
   c->isam_n = 0;
   c->isam_moved_valid = false; c->isam_H_valid = false; c->wild_valid = false;
-  c->isam_L_valid = false; c->isam_E_seen = c->isam_NI_seen = c->isam_NP_seen = 0;
+  drop_isam_step(c); c->isam_E_seen = c->isam_NI_seen = c->isam_NP_seen = 0;
   // the growth reserve belongs to the incremental driving mode: a context that leaves it (delete isam2) goes back to a
   // structure without phantom slots at its next use; the next fgo_isam2_update lays a fresh reserve down
   c->isam_incremental = false;

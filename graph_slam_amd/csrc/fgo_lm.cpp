@@ -39,6 +39,19 @@ void ba_off(fgo_ctx *c) {
   c->ba_disable = true;
   if (c->ba.on) c->structure_dirty = true;
 }
+hipError_t stage_lambda(fgo_ctx *c, double lambda) {
+  c->h_scal[3] = lambda;
+  const hipError_t e = hipMemcpyAsync(c->d_scal.p + 3, c->h_scal + 3, sizeof(double), hipMemcpyHostToDevice, c->stream);
+  return e != hipSuccess ? e : hipMemsetAsync(c->d_fail.p, 0, sizeof(int), c->stream);
+}
+void claim_L(fgo_ctx *c) { c->L_holds = LHolds::scratch; }
+void record_L(fgo_ctx *c, LHolds what) { c->L_holds = what; }
+void drop_undamped(fgo_ctx *c) {
+  if (c->L_holds == LHolds::undamped || c->L_holds == LHolds::undamped_sigma) c->L_holds = LHolds::scratch;
+}
+void drop_isam_step(fgo_ctx *c) {
+  if (c->L_holds == LHolds::isam_step) c->L_holds = LHolds::scratch;
+}
 
 void enqueue_trial(fgo_ctx *c, int cur, bool with_events) {
   const int cand = cur ^ 1;
@@ -61,9 +74,7 @@ void enqueue_trial(fgo_ctx *c, int cur, bool with_events) {
 }
 
 int run_trial(fgo_ctx *c, double lambda, double *chi_cand, double *scale, int *failed, fgo_stats *st) {
-  c->cov_factor_valid = false;
-  c->sinv.valid = false;
-  c->isam_L_valid = false;
+  claim_L(c);
   if (c->shard_world > 1) return run_trial_dist(c, lambda, chi_cand, scale, failed, st);
   hipStream_t s = c->stream;
   c->h_scal[3] = lambda;                                 // (read by the trial's first kernel node)
@@ -115,8 +126,7 @@ int run_trial(fgo_ctx *c, double lambda, double *chi_cand, double *scale, int *f
 
 int linearize_current(fgo_ctx *c, bool want_maxdiag) {
   hipStream_t s = c->stream;
-  c->cov_factor_valid = false;
-  c->sinv.valid = false;
+  drop_undamped(c);
   ctx_linearize(c, c->cur, c->d_scal.p + 0);
   { const int rc = dist_sum_scalars(c, 0, 1); if (rc) return rc; }                    // chi2: partial sums over the ranks' factors
   if (c->shard_world > 1) {                                                           // complete the gradient of the top

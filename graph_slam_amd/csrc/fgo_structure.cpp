@@ -978,7 +978,7 @@ struct StructureBuild {
     });
     HIPCHK(c, c->d_acc_desc.upload(ad, s));
   }
-  c->isam_L_valid = false;
+  claim_L(c);                                        // (d_L is re-allocated below)
   c->col_task.clear();
   if (c->isam_incremental && !dist) {               // partial sweeps: task of every column / accumulate target / column group
     const int ntask = (int)S.task_ptr.size() - 1;
@@ -1433,7 +1433,6 @@ struct StructureBuild {
   if (R > 0) { c->inc.E_cap = E_cap; c->inc.NI_cap = NI_cap; c->inc.valid = true; }
   c->built_N = N;
   c->cur = 0;
-  c->cov_factor_valid = false;
   c->sinv.release();                                  // the selected inversion's tables belong to the old structure
   c->h_pose_col.clear();
   c->structure_dirty = false;
@@ -1731,8 +1730,7 @@ int refresh_factors(fgo_ctx *c) {
   I.valid = true;
   c->structure_dirty = false;
   c->lin_valid = false;
-  c->cov_factor_valid = false;
-  c->sinv.valid = false;
+  drop_undamped(c);
   fgo_stats &st = c->last;
   st.structure_rebuilt = 0;
   st.t_symbolic = now_s() - t0;                                 // host time of the in-place extension

@@ -341,6 +341,43 @@ def test_partial_refactorisation_equals_full_sweep_bitwise(monkeypatch):
     assert sum(int(st.reserved[1]) for st in s1) > 0
 
 
+def test_factor_taken_between_updates_forces_a_full_sweep():
+    """The previous step's factor stays in d_L for the next update only while nothing else writes it: after a marginal
+    request, fgo_solve_step or fgo_bench_phase the next update re-factors everything and still ends where an undisturbed run
+    ends, bit for bit; after calls that leave d_L alone it stays partial.  A marginal request right after an update factors
+    the undamped system itself: it must not take the ISAM2 factor for that one."""
+    import ctypes as C
+    n0, extra = 5000, 12
+    g = synth_gtsam(n0 + extra, 5, 2, seed=23)
+    rng = np.random.default_rng(1)
+    g["poses"][n0 - 40:n0, :3] += rng.normal(size=(40, 3)) * 0.12
+    delta = np.zeros(6 * (n0 + extra))
+
+    def marginals(gr):
+        m = gr.marginal_cov_many([3, n0 - 7, 17, 17])
+        gr.linearize(dense=False)
+        assert np.array_equal(m, gr.marginal_cov_many([3, n0 - 7, 17, 17]))
+
+    def solve_step(gr):
+        gr._chk(G.lib.fgo_solve_step(gr._h, 1e-3, delta.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def preserve(gr):
+        gr.get_poses(); gr.chi2(); gr.linearize(dense=False)
+
+    calls = {n0 + 1: marginals, n0 + 3: preserve, n0 + 5: solve_step, n0 + 7: preserve, n0 + 9: lambda gr: gr.bench_phase(1, 1),
+             n0 + 10: preserve}
+    gr, stats = _grow(G.Graph, g, n0, extra, lambda gr, k: calls[k](gr) if k in calls else None)
+    plain, plain_stats = _grow(G.Graph, g, n0, extra)
+    assert all(int(st.reserved[3]) > 0 or int(st.reserved[3]) == -2 for st in plain_stats[1:])
+    for k, call in calls.items():
+        tasks = int(stats[k - n0 + 2].reserved[3])                         # the update after the call
+        assert (tasks > 0 or tasks == -2) if call is preserve else tasks == -1, (k - n0, tasks)
+    assert [int(st.reserved[1]) for st in stats] == [int(st.reserved[1]) for st in plain_stats]
+    np.testing.assert_array_equal(gr.get_poses(), plain.get_poses())
+    for a, b in zip(state_of(gr, n0 + extra), state_of(plain, n0 + extra)):
+        np.testing.assert_array_equal(a, b)
+
+
 def test_against_independent_isam2_reference():
     """The product against tests/isam2_reference.py -- per-factor cached linearisations, variable-wise relinearisation,
     elimination + back-substitution with the wildfire rule -- on a graph that grows by one pose per update.

@@ -175,6 +175,19 @@ def test_cache_determinism_refresh_and_growth():
     assert np.array_equal(a1, a1b)                                          # and on repeat
     pc = gr1.marginal_cov_pairs([5, 6], [6, 700])
     assert np.array_equal(pc, gr2.marginal_cov_pairs([5, 6], [6, 700]))
+
+    def requests():
+        return gr1.marginal_cov_all()[1], gr1.marginal_cov_many([29, 1, 7, 7, 700]), gr1.marginal_cov_pairs([5, 6, 1], [6, 700, 1100])
+    before = requests()
+    assert np.array_equal(before[1][2], before[1][3])                         # a repeated id
+    delta = np.zeros(6 * n)
+    # calls that write the resident factor (a damped one) or the linearisation at the same estimate: the next requests
+    # factor again and give the same bits
+    for call in (lambda: gr1._chk(G.lib.fgo_solve_step(gr1._h, 1e-3, delta.ctypes.data_as(C.POINTER(C.c_double)))),
+                 lambda: gr1.bench_phase(1, 1), lambda: gr1.linearize(dense=False)):
+        call()
+        for a, b in zip(before, requests()):
+            assert np.array_equal(a, b)
     gr1.optimize(1)
     _, a3 = gr1.marginal_cov_all()
     assert not np.array_equal(a3, a1)
