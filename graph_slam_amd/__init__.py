@@ -99,6 +99,9 @@ def _load():
     lib.fgo_marginal_cov_all.argtypes = [C.c_void_p, C.c_int64, i64p, dp]
     lib.fgo_marginal_cov_pairs.argtypes = [C.c_void_p, C.c_int64, i64p, i64p, dp]
     lib.fgo_debug_selinv_stats.argtypes = [C.c_void_p, dp]
+    lib.fgo_gate_edges_se3.argtypes = [C.c_void_p, C.c_int64, i64p, i64p, dp, dp, C.c_int, dp, dp, dp]
+    lib.fgo_edge_chi2_se3.argtypes = [C.c_void_p, C.c_int64, C.c_int64, dp]
+    lib.fgo_debug_gate_stats.argtypes = [C.c_void_p, dp]
     lib.fgo_dist_unique_id.argtypes = [C.c_void_p]
     lib.fgo_dist_init_rccl.argtypes = [C.c_void_p, C.c_void_p]
     lib.fgo_debug_partition.argtypes = [C.c_int, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
@@ -431,6 +434,34 @@ class Graph:
         self._chk(lib.fgo_debug_selinv_stats(self._h, _dp(out)))
         return dict(t_lists_s=out[0], list_bytes=int(out[1]), ms_factor=out[2], ms_prep=out[3], ms_sweep=out[4], entries=int(out[5]),
                     fallback_pairs=int(out[6]))
+
+    def gate_edges(self, a, b, meas7, info21, tangent_order=FGO_TANGENT_G2O, want_cov=False):
+        """(d2, chi2[, P]) of candidate SE3 edges a[k] -> b[k] at the current estimate; nothing is added to the graph.
+        d2: squared Mahalanobis distance of the innovation under the map's covariance (chi-square, 6 dof, for a correct
+        candidate), chi2 = e' Omega e, P[n, 6, 6] = [Ja Jb] Sigma [Ja Jb]'."""
+        a = np.ascontiguousarray(a, np.int64); b = np.ascontiguousarray(b, np.int64)
+        assert a.shape == b.shape and a.ndim == 1
+        n = len(a)
+        meas7 = np.ascontiguousarray(meas7, np.float64).reshape(n, 7); info21 = np.ascontiguousarray(info21, np.float64).reshape(n, 21)
+        d2 = np.zeros(n); chi2 = np.zeros(n)
+        P = np.zeros((n, 6, 6)) if want_cov else None
+        self._chk(lib.fgo_gate_edges_se3(self._h, n, _i64p(a), _i64p(b), _dp(meas7), _dp(info21), tangent_order, _dp(d2), _dp(chi2),
+                                         _dp(P) if want_cov else None))
+        return (d2, chi2, P) if want_cov else (d2, chi2)
+
+    def edge_chi2(self, first=0, n=None):
+        """e' Omega e of the SE3 edges [first, first + n) in the order they were added (n = None: all from `first`)"""
+        if n is None:
+            n = max(0, lib.fgo_num_edges(self._h) - first)
+        out = np.zeros(n)
+        self._chk(lib.fgo_edge_chi2_se3(self._h, first, n, _dp(out)))
+        return out
+
+    def gate_stats(self):
+        """figures of the last gate_edges call (fgo_debug_gate_stats)"""
+        out = np.zeros(4)
+        self._chk(lib.fgo_debug_gate_stats(self._h, _dp(out)))
+        return dict(off_pattern=int(out[0]), column_groups=int(out[1]), ms_kernel=out[2], ms_solves=out[3])
 
     def add_plane(self, pid, abcd):
         a = np.ascontiguousarray(abcd, np.float64)

@@ -328,6 +328,25 @@ struct SinvPlan {
 void launch_sinv_prep(const SinvPlan &Q, const double *Lv, double *U, hipStream_t s);
 void launch_sinv_sweep(const SinvPlan &Q, const HostSchedule &H, hipStream_t s);      // reverse levels, one workgroup per task
 void launch_sinv_gather(const int64_t *enc, int64_t n, const double *Sig, double *out, hipStream_t s);   // enc: block << 1 | transpose
-void launch_sinv_rows(const int *cols, int64_t n, const double *x, double *out, hipStream_t s);          // out[i] = x rows of column cols[i]
+// out[i * istride + r * rstride] = x[6 cols[i] + r]: the rows of a column solve at the block columns cols[i]
+void launch_sinv_rows(const int *cols, int64_t n, const double *x, double *out, hipStream_t s, int64_t istride = 6, int64_t rstride = 1);
+
+// ---- gating of candidate SE3 edges (kernels_gate.hip): residual, chi2 and the squared Mahalanobis distance of the innovation
+// under the map's covariance.  Covariance blocks are named by a code: >= 0 a block of the selected inverse (block << 1 | transpose),
+// GATE_ZERO a zero block (fixed endpoint), <= GATE_EXTRA0 a block of `extra` filled by column solves
+constexpr int64_t GATE_ZERO = -1, GATE_EXTRA0 = -2;
+inline int64_t gate_extra_code(int64_t slot, bool transpose) { return GATE_EXTRA0 - ((slot << 1) | (transpose ? 1 : 0)); }
+constexpr int GATE_REC = 28;    // doubles per candidate record: Z^-1 (t, q_xyzw), the 21 upper-triangular entries of the information
+struct GatePlan {
+  int64_t n;
+  const int *va, *vb;           // [n] variable (row of the value array) of either endpoint
+  const double *rec;            // [n][GATE_REC]
+  const int64_t *enc;           // [n][3] codes of Sigma_aa, Sigma_bb, Sigma_ab (rows a, columns b); unused without covariance
+  const double *Sig, *extra;    // the selected inverse; [slots][36] blocks off its pattern
+  double *out;                  // [n] d2 | [n] chi2 | [n] status (0 ok, 1 information not positive definite, 2 innovation covariance not) | [n][36] P
+  int want_P;
+};
+// one launch for all candidates; with_cov = false: residual only (d2 = chi2, no covariance block is read)
+void launch_gate(const GatePlan &A, const double *values, bool gtsam, bool with_cov, hipStream_t s);
 
 }  // namespace fgo

@@ -162,6 +162,14 @@ struct fgo_ctx {
       d_sptr.release(); d_enc.release(); d_sidx.release(); d_U.release(); d_Sig.release(); d_out.release();
     }
   } sinv;
+  // gating of candidate edges (fgo_marginals.cpp, kernels_gate.hip): staging of one request and the figures of the last one
+  struct Gate {
+    fgo::DevBuf<int> d_v, d_cols;
+    fgo::DevBuf<int64_t> d_enc;
+    fgo::DevBuf<double> d_rec, d_extra, d_out, d_rhs;
+    int64_t n_off = 0, n_groups = 0;   // candidates whose Sigma_ab was off the factor's pattern; block columns solved for them
+    double ms_kernel = 0, ms_solves = 0;
+  } gate;
   // ---- ISAM2 state (fgo_isam2_update): linearisation point and linear solution per variable, variable order
   fgo::DevBuf<double> d_theta, d_delta;  // 8 / 6 doubles per variable
   // partial re-factorisation (L_holds == isam_step): an update re-runs only the tasks on the paths from the affected variables

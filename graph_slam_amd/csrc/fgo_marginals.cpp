@@ -4,6 +4,8 @@
 //  - chosen diagonal blocks (fgo_marginal_cov, fgo_marginal_cov_many): column solves through that factor;
 //  - every diagonal block, and pairs (fgo_marginal_cov_all, fgo_marginal_cov_pairs): blocks of Sigma = H^-1 on the pattern
 //    of L by selected inversion (kernels_sinv.hip), recomputed once per factorisation; pairs off that pattern by column solves.
+//  - gating of candidate edges (fgo_gate_edges_se3): the same blocks, left on the device and consumed by kernels_gate.hip, which
+//    returns the squared Mahalanobis distance of each candidate's innovation; fgo_edge_chi2_se3 is its residual-only form.
 // The pair tables of the inversion are built on its first request after a structure build (never in the structure phase, so
 // neither the symbolic time nor the optimiser's timings move) and kept until the structure is rebuilt.
 #include "fgo_ctx.hpp"
@@ -73,6 +75,22 @@ int undamped_factor(fgo_ctx *c) {
   return FGO_OK;
 }
 
+// The six columns of H^-1 at block column cb, one after the other through the undamped factor: after(k) is enqueued behind the
+// solve of column 6 cb + k, whose solution d_x then holds.  rhs: 6 nb doubles of scratch.
+template <class F>
+int solve_block_column(fgo_ctx *c, DevBuf<double> &rhs, int cb, F &&after) {
+  hipStream_t s = c->stream;
+  const int nb = c->plan.nb;
+  for (int k = 0; k < 6; ++k) {
+    HIPCHK(c, hipMemsetAsync(rhs.p, 0, sizeof(double) * (size_t)nb * 6, s));
+    const double one = 1.0;
+    HIPCHK(c, hipMemcpyAsync(rhs.p + 6 * (size_t)cb + k, &one, sizeof(double), hipMemcpyHostToDevice, s));
+    launch_solve(c->plan, c->sched, c->d_L.p, rhs.p, c->d_x.p, s);
+    after(k);
+  }
+  return FGO_OK;
+}
+
 // Blocks (a, b) of H^-1 through the undamped factor, for the queries q grouped by the column of b (by_b), a's column of every
 // query in col_a.  Per column b: six unit right-hand sides, each solved and the rows of the group's a-columns gathered, then one
 // copy and one synchronisation.  cov36[q]: rows in a's tangent, columns in b's.
@@ -93,19 +111,32 @@ int column_solves(fgo_ctx *c, const std::map<int, std::vector<int64_t>> &by_b, c
     for (int64_t i = 0; i < na; ++i) cols[(size_t)i] = col_a[(size_t)qs[(size_t)i]];
     HIPCHK(c, d_cols.upload(cols, s));
     HIPCHK(c, rows.alloc((size_t)na * 36));
-    for (int k = 0; k < 6; ++k) {                              // column 6 cb + k of H^-1: only the a-columns' rows come back
-      HIPCHK(c, hipMemsetAsync(rhs.p, 0, sizeof(double) * (size_t)nb * 6, s));
-      const double one = 1.0;
-      HIPCHK(c, hipMemcpyAsync(rhs.p + 6 * (size_t)cb + k, &one, sizeof(double), hipMemcpyHostToDevice, s));
-      launch_solve(c->plan, c->sched, c->d_L.p, rhs.p, c->d_x.p, s);
-      launch_sinv_rows(d_cols.p, na, c->d_x.p, rows.p + (size_t)k * na * 6, s);
-    }
+    // column 6 cb + k of H^-1: only the a-columns' rows come back
+    const int rc = solve_block_column(c, rhs, cb, [&](int k) { launch_sinv_rows(d_cols.p, na, c->d_x.p, rows.p + (size_t)k * na * 6, s); });
+    if (rc) return rc;
     h_rows.resize((size_t)na * 36);
     HIPCHK(c, hipMemcpyAsync(h_rows.data(), rows.p, sizeof(double) * h_rows.size(), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     for (int64_t i = 0; i < na; ++i)
       for (int k = 0; k < 6; ++k)
         for (int r = 0; r < 6; ++r) cov36[36 * qs[(size_t)i] + r * 6 + k] = h_rows[((size_t)k * na + i) * 6 + r];
+  }
+  HIPCHK(c, hipGetLastError());
+  return FGO_OK;
+}
+
+// The same solves with the blocks left on the device: slot t of `blocks` (row-major 6x6) = rows of column row_col[t], columns of
+// the group's column.  by_col: slots grouped by the solved column.  No copy, no synchronisation (rhs, d_cols: the caller's scratch).
+int column_solves_resident(fgo_ctx *c, const std::map<int, std::vector<int64_t>> &by_col, const std::vector<int> &row_col,
+                           DevBuf<double> &rhs, DevBuf<int> &d_cols, double *blocks) {
+  if (by_col.empty()) return FGO_OK;
+  hipStream_t s = c->stream;
+  HIPCHK(c, rhs.alloc((size_t)c->plan.nb * 6));
+  HIPCHK(c, d_cols.upload(row_col, s));                            // (slots are numbered group after group: a group is a range)
+  for (const auto &grp : by_col) {
+    const int64_t t0 = grp.second.front(), nt = (int64_t)grp.second.size();
+    const int rc = solve_block_column(c, rhs, grp.first, [&](int k) { launch_sinv_rows(d_cols.p + t0, nt, c->d_x.p, blocks + 36 * t0 + k, s, 36, 6); });
+    if (rc) return rc;
   }
   HIPCHK(c, hipGetLastError());
   return FGO_OK;
@@ -208,6 +239,17 @@ int sigma_ready(fgo_ctx *c) {
   return FGO_OK;
 }
 
+// Where Cov(a, b) sits in Sigma for the columns ca, cb: block << 1 | transpose, or -1 off the pattern of L.  Block (hi, lo) of
+// Sigma holds rows of the later column -- transposed when a is the earlier one
+int64_t pattern_code(const Symbolic &S, int ca, int cb) {
+  if (ca == cb) return S.colptr[ca] << 1;
+  const int lo = std::min(ca, cb), hi = std::max(ca, cb);
+  const int *r0 = S.rowidx.data() + S.colptr[lo] + 1, *r1 = S.rowidx.data() + S.colptr[lo + 1];
+  const int *t = std::lower_bound(r0, r1, hi);
+  if (t == r1 || *t != hi) return -1;
+  return ((int64_t)(t - S.rowidx.data()) << 1) | (ca == lo ? 1 : 0);
+}
+
 // blocks of Sigma named by enc (block << 1 | transpose) -> out (n x 36)
 int selinv_fetch(fgo_ctx *c, const std::vector<int64_t> &enc, double *out) {
   if (enc.empty()) return FGO_OK;
@@ -284,22 +326,12 @@ int fgo_marginal_cov_pairs(fgo_ctx *c, int64_t n, const int64_t *id_a, const int
   if ((rc = host_pose_cols(c)) != FGO_OK) return rc;
   std::vector<int> col(idx.size());
   for (size_t q = 0; q < idx.size(); ++q) col[q] = c->h_pose_col[idx[q]];
-  const Symbolic &S = c->S;
-  // pairs on the pattern of L: block (hi, lo) of Sigma holds rows of the later column -- transposed when a is the earlier one
   std::vector<int64_t> enc, on_pat;
-  std::map<int, std::vector<int64_t>> by_b;                       // the others, by b's column
+  std::map<int, std::vector<int64_t>> by_b;                       // the pairs off the pattern of L, by b's column
   for (int64_t q = 0; q < n; ++q) {
-    const int ca = col[(size_t)q], cb = col[(size_t)(n + q)];
-    if (ca == cb) { enc.push_back(S.colptr[ca] << 1); on_pat.push_back(q); continue; }
-    const int lo = std::min(ca, cb), hi = std::max(ca, cb);
-    const int *r0 = S.rowidx.data() + S.colptr[lo] + 1, *r1 = S.rowidx.data() + S.colptr[lo + 1];
-    const int *t = std::lower_bound(r0, r1, hi);
-    if (t != r1 && *t == hi) {
-      enc.push_back(((int64_t)(t - S.rowidx.data()) << 1) | (ca == lo ? 1 : 0));
-      on_pat.push_back(q);
-    } else {
-      by_b[cb].push_back(q);
-    }
+    const int64_t code = pattern_code(c->S, col[(size_t)q], col[(size_t)(n + q)]);
+    if (code >= 0) { enc.push_back(code); on_pat.push_back(q); }
+    else by_b[col[(size_t)(n + q)]].push_back(q);
   }
   std::vector<double> blk(enc.size() * 36);
   if ((rc = selinv_fetch(c, enc, blk.data())) != FGO_OK) return rc;
@@ -317,6 +349,186 @@ int fgo_debug_selinv_stats(const fgo_ctx *c, double out[7]) {
   out[4] = c->sinv.ms_sweep;
   out[5] = (double)c->sinv.n_entries;
   out[6] = (double)c->sinv.n_fallback;
+  return FGO_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// e, chi2 and (with_cov) d2 / P of n staged candidates in ONE launch, then one copy and one synchronisation.  va / vb: variable of
+// either endpoint, rec: GATE_REC doubles per candidate, enc: three covariance codes per candidate (with_cov only).
+// out: [n] d2 | [n] chi2 | [n] status | [n][36] P (want_P)
+int run_gate(fgo_ctx *c, int64_t n, const std::vector<int> &vab, const std::vector<double> &rec, const std::vector<int64_t> &enc, bool with_cov,
+             bool want_P, std::vector<double> &out) {
+  hipStream_t s = c->stream;
+  fgo_ctx::Gate &G = c->gate;
+  HIPCHK(c, G.d_v.upload(vab, s));
+  HIPCHK(c, G.d_rec.upload(rec, s));
+  if (with_cov) HIPCHK(c, G.d_enc.upload(enc, s));
+  out.resize((size_t)n * (want_P ? 39 : 3));
+  HIPCHK(c, G.d_out.alloc(out.size()));
+  GatePlan A{};
+  A.n = n;
+  A.va = G.d_v.p; A.vb = G.d_v.p + n;
+  A.rec = G.d_rec.p;
+  A.enc = G.d_enc.p;
+  A.Sig = c->sinv.d_Sig.p; A.extra = G.d_extra.p;
+  A.out = G.d_out.p;
+  A.want_P = want_P ? 1 : 0;
+  HIPCHK(c, hipEventRecord(c->ev[2], s));
+  launch_gate(A, c->d_poses[c->cur].p, c->gtsam_mode, with_cov, s);
+  HIPCHK(c, hipEventRecord(c->ev[3], s));
+  HIPCHK(c, hipMemcpyAsync(out.data(), G.d_out.p, sizeof(double) * out.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  float ms = 0;
+  HIPCHK(c, hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+  G.ms_kernel = ms;
+  return FGO_OK;
+}
+
+// the record of one candidate / edge: inverse measurement (unit quaternion), information
+void gate_record(const double *meas7, const double *info21, double *rec) {
+  const double *q = meas7 + 3;
+  const double nq = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  const double z[7] = {meas7[0], meas7[1], meas7[2], q[0] / nq, q[1] / nq, q[2] / nq, q[3] / nq};
+  pose_inv7(z, rec);
+  std::memcpy(rec + 7, info21, 21 * sizeof(double));
+}
+
+}  // namespace
+
+extern "C" {
+
+int fgo_gate_edges_se3(fgo_ctx *c, int64_t n, const int64_t *id_a, const int64_t *id_b, const double *meas7, const double *info_ut21,
+                       int tangent_order, double *d2_out, double *chi2_out, double *pred_cov36_out) try {
+  if (!c || n < 0) return FGO_EINVAL;
+  if (n == 0) return FGO_OK;
+  if (!id_a || !id_b || !meas7 || !info_ut21 || !d2_out) return FGO_EINVAL;
+  if (tangent_order != FGO_TANGENT_G2O && tangent_order != FGO_TANGENT_GTSAM) return fail(c, FGO_EINVAL, "bad tangent order");
+  const auto at = [](int64_t q) { return "candidate " + std::to_string(q) + ": "; };
+  std::vector<int> vab((size_t)(2 * n));
+  for (int64_t q = 0; q < n; ++q) {
+    const auto a = c->id2idx.find(id_a[q]), b = c->id2idx.find(id_b[q]);
+    if (a == c->id2idx.end() || b == c->id2idx.end()) return fail(c, FGO_EINVAL, at(q) + "unknown variable id");
+    if (a->second == b->second) return fail(c, FGO_EINVAL, at(q) + "edge endpoints must differ");
+    if (c->var_kind[a->second] != 0 || c->var_kind[b->second] != 0) return fail(c, FGO_EINVAL, at(q) + "SE3 edges connect poses");
+    const double *qz = meas7 + 7 * q + 3;
+    if (!(qz[0] * qz[0] + qz[1] * qz[1] + qz[2] * qz[2] + qz[3] * qz[3] > 0)) return fail(c, FGO_EINVAL, at(q) + "zero quaternion");
+    vab[(size_t)q] = a->second; vab[(size_t)(n + q)] = b->second;
+  }
+  int rc = common_checks(c);
+  if (rc) return rc;
+  if ((tangent_order == FGO_TANGENT_GTSAM) != c->gtsam_mode)
+    return fail(c, FGO_EINVAL, "candidate edges must use the tangent order of the context's own semantics");
+  std::vector<int> idx;                                           // the free endpoints
+  for (int v : vab)
+    if (!c->fixed[v]) idx.push_back(v);
+  fgo_ctx::Gate &G = c->gate;
+  G.n_off = G.n_groups = 0;
+  G.ms_solves = 0;
+  std::vector<int64_t> enc;
+  const bool with_cov = !idx.empty();                             // (every endpoint fixed: P = 0, no factorisation)
+  if (with_cov) {
+    if ((rc = ensure_columns(c, &idx)) != FGO_OK) return rc;
+    if ((rc = sigma_ready(c)) != FGO_OK) return rc;
+    if ((rc = host_pose_cols(c)) != FGO_OK) return rc;
+    const Symbolic &S = c->S;
+    enc.assign((size_t)(3 * n), GATE_ZERO);
+    std::vector<int64_t> off;                                     // candidates whose Sigma_ab is off the pattern of L
+    for (int64_t q = 0; q < n; ++q) {
+      const int va = vab[(size_t)q], vb = vab[(size_t)(n + q)];
+      const int ca = c->fixed[va] ? -1 : c->h_pose_col[va], cb = c->fixed[vb] ? -1 : c->h_pose_col[vb];
+      if (ca >= 0) enc[(size_t)(3 * q)] = S.colptr[ca] << 1;
+      if (cb >= 0) enc[(size_t)(3 * q + 1)] = S.colptr[cb] << 1;
+      if (ca < 0 || cb < 0) continue;
+      const int64_t code = pattern_code(S, ca, cb);
+      if (code >= 0) enc[(size_t)(3 * q + 2)] = code; else off.push_back(q);
+    }
+    if (!off.empty()) {
+      // Sigma_ab = Sigma_ba^T: solve for the columns of whichever side has fewer distinct ones among these candidates (many old
+      // poses against the newest one: one group, whichever way round the pairs were written)
+      std::map<int, std::vector<int64_t>> by_a, by_b;
+      for (int64_t q : off) {
+        by_a[c->h_pose_col[vab[(size_t)q]]].push_back(q);
+        by_b[c->h_pose_col[vab[(size_t)(n + q)]]].push_back(q);
+      }
+      const bool solve_a = by_a.size() < by_b.size();
+      std::map<int, std::vector<int64_t>> by_col;                 // slots of the device buffer, numbered group after group
+      std::vector<int> row_col;
+      for (const auto &grp : solve_a ? by_a : by_b) {
+        std::vector<int64_t> &slots = by_col[grp.first];
+        for (int64_t q : grp.second) {
+          const int64_t t = (int64_t)row_col.size();
+          slots.push_back(t);
+          row_col.push_back(c->h_pose_col[vab[(size_t)(solve_a ? n + q : q)]]);
+          // solved for b's columns: the slot holds rows a, columns b; for a's: rows b, columns a = Sigma_ab^T
+          enc[(size_t)(3 * q + 2)] = gate_extra_code(t, solve_a);
+        }
+      }
+      hipStream_t s = c->stream;
+      HIPCHK(c, G.d_extra.alloc(row_col.size() * 36));
+      HIPCHK(c, hipEventRecord(c->ev[0], s));
+      if ((rc = column_solves_resident(c, by_col, row_col, G.d_rhs, G.d_cols, G.d_extra.p)) != FGO_OK) return rc;
+      HIPCHK(c, hipEventRecord(c->ev[1], s));
+      G.n_off = (int64_t)off.size();
+      G.n_groups = (int64_t)by_col.size();
+    }
+  }
+  std::vector<double> rec((size_t)n * GATE_REC), out;
+  for (int64_t q = 0; q < n; ++q) gate_record(meas7 + 7 * q, info_ut21 + 21 * q, &rec[(size_t)q * GATE_REC]);
+  if ((rc = run_gate(c, n, vab, rec, enc, with_cov, with_cov && pred_cov36_out, out)) != FGO_OK) return rc;
+  if (G.n_groups > 0) {
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    G.ms_solves = ms;
+  }
+  for (int64_t q = 0; q < n; ++q) {
+    const double st = out[(size_t)(2 * n + q)];
+    if (st == 1.0) return fail(c, FGO_ENUM, at(q) + "information matrix not positive definite");
+    if (st != 0.0) return fail(c, FGO_ENUM, at(q) + "innovation covariance not positive definite");
+  }
+  std::memcpy(d2_out, out.data(), sizeof(double) * (size_t)n);
+  if (chi2_out) std::memcpy(chi2_out, out.data() + n, sizeof(double) * (size_t)n);
+  if (pred_cov36_out) {
+    if (with_cov) std::memcpy(pred_cov36_out, out.data() + 3 * n, sizeof(double) * 36 * (size_t)n);
+    else std::memset(pred_cov36_out, 0, sizeof(double) * 36 * (size_t)n);
+  }
+  return FGO_OK;
+} FGO_CATCH_INT(c)
+
+int fgo_edge_chi2_se3(fgo_ctx *c, int64_t first, int64_t n, double *chi2_out) try {
+  if (!c || first < 0 || n < 0 || (n > 0 && !chi2_out)) return FGO_EINVAL;
+  std::vector<int64_t> edges;                                     // the SE3 edges [first, first + n) of the store
+  int64_t k = 0;
+  for (size_t e = 0; e < c->torder.size() && (int64_t)edges.size() < n; ++e) {
+    if (c->torder[e] > FGO_TANGENT_GTSAM) continue;
+    if (k++ >= first) edges.push_back((int64_t)e);
+  }
+  if ((int64_t)edges.size() < n) return fail(c, FGO_EINVAL, "fgo_edge_chi2_se3: the graph has fewer SE3 edges than first + n");
+  if (n == 0) return FGO_OK;
+  const int rc = common_checks(c);
+  if (rc) return rc;
+  std::vector<int> vab((size_t)(2 * n));
+  std::vector<double> rec((size_t)n * GATE_REC), out;
+  for (int64_t q = 0; q < n; ++q) {
+    const size_t e = (size_t)edges[(size_t)q];
+    vab[(size_t)q] = c->ei[e]; vab[(size_t)(n + q)] = c->ej[e];
+    gate_record(&c->meas[e * 7], &c->info[e * 21], &rec[(size_t)q * GATE_REC]);
+  }
+  const int rg = run_gate(c, n, vab, rec, std::vector<int64_t>(), false, false, out);
+  if (rg) return rg;
+  std::memcpy(chi2_out, out.data() + n, sizeof(double) * (size_t)n);
+  return FGO_OK;
+} FGO_CATCH_INT(c)
+
+int fgo_debug_gate_stats(const fgo_ctx *c, double out[4]) {
+  if (!c || !out) return FGO_EINVAL;
+  out[0] = (double)c->gate.n_off;
+  out[1] = (double)c->gate.n_groups;
+  out[2] = c->gate.ms_kernel;
+  out[3] = c->gate.ms_solves;
   return FGO_OK;
 }
 

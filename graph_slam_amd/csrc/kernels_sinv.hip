@@ -154,13 +154,14 @@ __global__ __launch_bounds__(256) void k_sinv_gather(const int64_t *__restrict__
   out[t] = (code & 1) ? B[(e % 6) * 6 + e / 6] : B[e];
 }
 
-// out[i][r] = x[6 cols[i] + r]: the rows of a column solve that a group of off-pattern pairs needs
+// out[i * istride + r * rstride] = x[6 cols[i] + r]: the rows of a column solve that a group of off-pattern pairs needs (6 / 1:
+// packed for the copy to the host; 36 / 6: column k of row-major blocks that stay on the device, out offset by k)
 __global__ __launch_bounds__(256) void k_sinv_rows(const int *__restrict__ cols, int64_t n, const double *__restrict__ x,
-                                                   double *__restrict__ out) {
+                                                   double *__restrict__ out, int64_t istride, int64_t rstride) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n * 6) return;
-  const int64_t i = t / 6;
-  out[t] = x[6 * (int64_t)cols[i] + (t - 6 * i)];
+  const int64_t i = t / 6, r = t - 6 * i;
+  out[i * istride + r * rstride] = x[6 * (int64_t)cols[i] + r];
 }
 
 }  // namespace
@@ -187,8 +188,8 @@ void launch_sinv_gather(const int64_t *enc, int64_t n, const double *Sig, double
   if (n > 0) hipLaunchKernelGGL(k_sinv_gather, dim3((unsigned)((n * 36 + 255) / 256)), dim3(256), 0, s, enc, n, Sig, out);
 }
 
-void launch_sinv_rows(const int *cols, int64_t n, const double *x, double *out, hipStream_t s) {
-  if (n > 0) hipLaunchKernelGGL(k_sinv_rows, dim3((unsigned)((n * 6 + 255) / 256)), dim3(256), 0, s, cols, n, x, out);
+void launch_sinv_rows(const int *cols, int64_t n, const double *x, double *out, hipStream_t s, int64_t istride, int64_t rstride) {
+  if (n > 0) hipLaunchKernelGGL(k_sinv_rows, dim3((unsigned)((n * 6 + 255) / 256)), dim3(256), 0, s, cols, n, x, out, istride, rstride);
 }
 
 }  // namespace fgo

@@ -250,6 +250,31 @@ int fgo_marginal_cov_pairs(fgo_ctx *ctx, int64_t n, const int64_t *id_a, const i
  * factorisation, [3] of the prep kernel, [4] of the reverse sweep, [5] pair-table entries, [6] pairs of the last
  * fgo_marginal_cov_pairs call that were off the factor's pattern (served by column solves) */
 int fgo_debug_selinv_stats(const fgo_ctx *ctx, double out[7]);
+/* ---- validating an edge BEFORE it enters the graph, inspecting edges afterwards.  The reference asks "is this constraint
+ *      consistent with the map, given how uncertain the map is?" in several places and approximates the answer each time, because
+ *      a Marginals object costs it a batch factorisation: the chi2_for_vro switch gates a visual-odometry edge with
+ *      utils::chi2(N, 0.95) against an ad-hoc rotation-only information matrix (gtsam/test_vro_imu_graph.cpp:679-778); plane
+ *      association builds a Marginals object and then has the J Sigma J' test commented out in favour of fixed thresholds
+ *      (gtsam/gtsam_graph.cpp:1357-1470); a commented-out robust kernel is the only defence against a bad loop closure
+ *      (g2o/g2o_graph.cpp:130).  Here the exact test is one call.  For a candidate between a and b with measurement Z and
+ *      information Omega (positive definite), at the current estimate: e, Ja, Jb as the linearisation computes them for a real
+ *      edge of the context's semantics; chi2 = e' Omega e; P = [Ja Jb] Sigma_{ab,ab} [Ja Jb]' with Sigma = (J' Omega J)^-1 of
+ *      the graph (the blocks fgo_marginal_cov_pairs returns; a fixed endpoint contributes zero blocks, both fixed: P = 0);
+ *      d2 = e' (P + Omega^-1)^-1 e, the squared Mahalanobis distance of the innovation: chi-square with 6 degrees of freedom
+ *      for a correct candidate that is not in the graph yet, 0 <= d2 <= chi2.  Accept when d2 < utils::chi2(6, 0.95) = 12.59.
+ * n candidate SE3 edges at the current estimate; nothing is added to the graph.  d2_out[n]; chi2_out[n] and
+ *      pred_cov36_out[n x 36] (P, row-major) may be NULL.  tangent_order must be the context's own semantics.
+ *      FGO_EINVAL: unknown id, non-pose variable, a == b, foreign tangent order; FGO_ENUM: an information matrix is not positive
+ *      definite (fgo_last_error names the first such candidate); FGO_ESTATE in distributed mode. */
+int fgo_gate_edges_se3(fgo_ctx *ctx, int64_t n, const int64_t *id_a, const int64_t *id_b, const double *meas7,
+                       const double *info_ut21, int tangent_order,
+                       double *d2_out, double *chi2_out, double *pred_cov36_out);
+/* e' Omega e of the SE3 edges already in the graph, [first, first + n) in the order they were added (g2o: edge->chi2()); needs no
+ *      factorisation.  Single-GPU entry point like the gate. */
+int fgo_edge_chi2_se3(fgo_ctx *ctx, int64_t first, int64_t n, double *chi2_out);
+/* [0] candidates of the last gate call whose Sigma_ab was off the factor's pattern, [1] column groups solved for them,
+ *      [2] device ms of the gate kernel, [3] device ms of those column solves */
+int fgo_debug_gate_stats(const fgo_ctx *ctx, double out[4]);
 
 /* ---- solve: ONE SparseOptimizer::optimize(max_iters) call as issued by
  *      CGraphG2O::optimizeGraph (g2o/g2o_graph.cpp:246-249).  Returns the number of LM iterations
