@@ -102,6 +102,8 @@ def _load():
     lib.fgo_gate_edges_se3.argtypes = [C.c_void_p, C.c_int64, i64p, i64p, dp, dp, C.c_int, dp, dp, dp]
     lib.fgo_edge_chi2_se3.argtypes = [C.c_void_p, C.c_int64, C.c_int64, dp]
     lib.fgo_debug_gate_stats.argtypes = [C.c_void_p, dp]
+    lib.fgo_gate_plane_factors.argtypes = [C.c_void_p, C.c_int64, i64p, i64p, dp, dp, dp, dp, dp, dp, dp]
+    lib.fgo_associate_planes.argtypes = [C.c_void_p, C.c_int64, C.c_int64, dp, dp, C.c_int64, i64p, C.c_double, C.c_double, i64p, dp, dp]
     lib.fgo_dist_unique_id.argtypes = [C.c_void_p]
     lib.fgo_dist_init_rccl.argtypes = [C.c_void_p, C.c_void_p]
     lib.fgo_debug_partition.argtypes = [C.c_int, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
@@ -457,8 +459,41 @@ class Graph:
         self._chk(lib.fgo_edge_chi2_se3(self._h, first, n, _dp(out)))
         return out
 
+    def gate_plane_factors(self, pose, plane, z, cov6, want_cov=False, want_resid=False):
+        """(d2, chi2, cos[, P][, e]) of candidate plane observations pose[k] -> plane[k] at the current estimate (GTSAM semantics);
+        nothing is added to the graph.  z[n, 4]: measured plane in the pose frame, cov6[n, 6]: upper triangle of its 3x3 covariance,
+        both as add_plane_factor takes them.  d2: squared Mahalanobis distance of the innovation under the map's covariance
+        (chi-square, 3 dof, for a correct association), chi2 = e' S^-1 e, cos: cosine between predicted and measured normal,
+        P[n, 3, 3] = [Jx Jp] Sigma [Jx Jp]', e[n, 3] the residual."""
+        pose = np.ascontiguousarray(pose, np.int64); plane = np.ascontiguousarray(plane, np.int64)
+        assert pose.shape == plane.shape and pose.ndim == 1
+        n = len(pose)
+        z = np.ascontiguousarray(z, np.float64).reshape(n, 4); cov6 = np.ascontiguousarray(cov6, np.float64).reshape(n, 6)
+        d2 = np.zeros(n); chi2 = np.zeros(n); cos = np.zeros(n)
+        P = np.zeros((n, 3, 3)) if want_cov else None
+        e = np.zeros((n, 3)) if want_resid else None
+        self._chk(lib.fgo_gate_plane_factors(self._h, n, _i64p(pose), _i64p(plane), _dp(z), _dp(cov6), _dp(d2), _dp(chi2), _dp(cos),
+                                             _dp(e) if want_resid else None, _dp(P) if want_cov else None))
+        return (d2, chi2, cos) + ((P,) if want_cov else ()) + ((e,) if want_resid else ())
+
+    def associate_planes(self, pose, z, cov6, plane_ids, d2_gate=7.815, cos_min=-1.0, want_matrix=False):
+        """(match, best2[, d2_matrix]): k plane observations z[k, 4] / cov6[k, 6] made from `pose` against the distinct planes
+        plane_ids[m].  match[k]: the plane with the smallest d2 if that is < d2_gate (7.815 = chi-square 3 dof, 95 %), else -1;
+        best2[k, 2]: smallest and second smallest d2 (+inf when absent); d2_matrix[k, m]: +inf where cos < cos_min or a covariance
+        is not positive definite.  A tie goes to the earlier entry of plane_ids."""
+        z = np.ascontiguousarray(z, np.float64).reshape(-1, 4)
+        k = len(z)
+        cov6 = np.ascontiguousarray(cov6, np.float64).reshape(k, 6)
+        plane_ids = np.ascontiguousarray(plane_ids, np.int64).reshape(-1)
+        m = len(plane_ids)
+        match = np.full(k, -1, np.int64); best2 = np.full((k, 2), np.inf)
+        D = np.full((k, m), np.inf) if want_matrix else None
+        self._chk(lib.fgo_associate_planes(self._h, int(pose), k, _dp(z), _dp(cov6), m, _i64p(plane_ids), d2_gate, cos_min,
+                                           _i64p(match), _dp(best2), _dp(D) if want_matrix else None))
+        return (match, best2, D) if want_matrix else (match, best2)
+
     def gate_stats(self):
-        """figures of the last gate_edges call (fgo_debug_gate_stats)"""
+        """figures of the last gate call of either kind (fgo_debug_gate_stats)"""
         out = np.zeros(4)
         self._chk(lib.fgo_debug_gate_stats(self._h, _dp(out)))
         return dict(off_pattern=int(out[0]), column_groups=int(out[1]), ms_kernel=out[2], ms_solves=out[3])

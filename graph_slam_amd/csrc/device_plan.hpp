@@ -349,4 +349,23 @@ struct GatePlan {
 // one launch for all candidates; with_cov = false: residual only (d2 = chi2, no covariance block is read)
 void launch_gate(const GatePlan &A, const double *values, bool gtsam, bool with_cov, hipStream_t s);
 
+// ---- gating of candidate plane observations (kernels_plane_gate.hip; GTSAM semantics): the same test for an OrientedPlane3
+// factor between a pose and a plane that is already a variable.  Covariance codes as above; a candidate whose codes are all
+// GATE_ZERO (both endpoints fixed) reads no covariance: P = 0
+constexpr int PGATE_REC = 10;   // doubles per candidate record: measured unit normal, offset, upper triangle of the 3x3 covariance S
+struct PlaneGatePlan {
+  int64_t n;
+  const int *vx, *vp;           // [n] variable (row of the value array) of the pose / of the plane
+  const double *rec;            // [n][PGATE_REC]
+  const int64_t *enc;           // [n][3] codes of Sigma_xx, Sigma_pp, Sigma_xp (rows: pose, columns: plane)
+  const double *Sig, *extra;    // the selected inverse; [slots][36] blocks off its pattern
+  double *out;                  // [n] d2 | [n] chi2 | [n] cos | [n] status (0 ok, 1 S not positive definite, 2 P + S not) | [n][3] e | [n][9] P (want_P)
+  int want_P;
+};
+void launch_plane_gate(const PlaneGatePlan &A, const double *values, hipStream_t s);
+// association of k observations from one pose with m planes: gate_out = the output above of the k m candidates, candidate j k + i
+// = observation i against plane j (the observations of one pair are neighbours: they share its covariance blocks).  res: [k]
+// position of the match in the plane list or -1 | [k][2] smallest, second smallest d2 (+inf when absent) | [k][m] d2 (want_matrix)
+void launch_plane_assoc(const double *gate_out, int64_t k, int64_t m, double d2_gate, double cos_min, bool want_matrix, double *res, hipStream_t s);
+
 }  // namespace fgo

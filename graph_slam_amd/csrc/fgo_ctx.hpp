@@ -166,7 +166,7 @@ struct fgo_ctx {
   struct Gate {
     fgo::DevBuf<int> d_v, d_cols;
     fgo::DevBuf<int64_t> d_enc;
-    fgo::DevBuf<double> d_rec, d_extra, d_out, d_rhs;
+    fgo::DevBuf<double> d_rec, d_extra, d_out, d_rhs, d_res;   // (d_res: result of a plane association)
     int64_t n_off = 0, n_groups = 0;   // candidates whose Sigma_ab was off the factor's pattern; block columns solved for them
     double ms_kernel = 0, ms_solves = 0;
   } gate;

@@ -6,8 +6,11 @@
 //    of L by selected inversion (kernels_sinv.hip), recomputed once per factorisation; pairs off that pattern by column solves.
 //  - gating of candidate edges (fgo_gate_edges_se3): the same blocks, left on the device and consumed by kernels_gate.hip, which
 //    returns the squared Mahalanobis distance of each candidate's innovation; fgo_edge_chi2_se3 is its residual-only form.
+//  - gating and association of plane observations (fgo_gate_plane_factors, fgo_associate_planes): the same host steps for a
+//    (pose, plane) pair, consumed by kernels_plane_gate.hip.
 // The pair tables of the inversion are built on its first request after a structure build (never in the structure phase, so
 // neither the symbolic time nor the optimiser's timings move) and kept until the structure is rebuilt.
+#include <set>
 #include "fgo_ctx.hpp"
 
 using namespace fgo;
@@ -388,6 +391,67 @@ int run_gate(fgo_ctx *c, int64_t n, const std::vector<int> &vab, const std::vect
   return FGO_OK;
 }
 
+// The covariance blocks of n candidates between the variables vab[q] (a) and vab[n + q] (b): enc = three codes per candidate
+// (Sigma_aa, Sigma_bb, Sigma_ab; GATE_ZERO for a fixed endpoint), the blocks off the pattern of L solved into gate.d_extra, and the
+// gate's figures reset / filled.  with_cov = false: every endpoint is fixed, P = 0 and nothing was factored.  The solves' time is
+// between ev[0] and ev[1] when gate.n_groups > 0 (read after the caller's synchronisation).
+int gate_blocks(fgo_ctx *c, int64_t n, const std::vector<int> &vab, std::vector<int64_t> &enc, bool &with_cov) {
+  int rc;
+  std::vector<int> idx;                                           // the free endpoints
+  for (int v : vab)
+    if (!c->fixed[v]) idx.push_back(v);
+  fgo_ctx::Gate &G = c->gate;
+  G.n_off = G.n_groups = 0;
+  G.ms_solves = 0;
+  enc.clear();
+  with_cov = !idx.empty();                                        // (every endpoint fixed: P = 0, no factorisation)
+  if (!with_cov) return FGO_OK;
+  if ((rc = ensure_columns(c, &idx)) != FGO_OK) return rc;
+  if ((rc = sigma_ready(c)) != FGO_OK) return rc;
+  if ((rc = host_pose_cols(c)) != FGO_OK) return rc;
+  const Symbolic &S = c->S;
+  enc.assign((size_t)(3 * n), GATE_ZERO);
+  std::vector<int64_t> off;                                       // candidates whose Sigma_ab is off the pattern of L
+  for (int64_t q = 0; q < n; ++q) {
+    const int va = vab[(size_t)q], vb = vab[(size_t)(n + q)];
+    const int ca = c->fixed[va] ? -1 : c->h_pose_col[va], cb = c->fixed[vb] ? -1 : c->h_pose_col[vb];
+    if (ca >= 0) enc[(size_t)(3 * q)] = S.colptr[ca] << 1;
+    if (cb >= 0) enc[(size_t)(3 * q + 1)] = S.colptr[cb] << 1;
+    if (ca < 0 || cb < 0) continue;
+    const int64_t code = pattern_code(S, ca, cb);
+    if (code >= 0) enc[(size_t)(3 * q + 2)] = code; else off.push_back(q);
+  }
+  if (off.empty()) return FGO_OK;
+  // Sigma_ab = Sigma_ba^T: solve for the columns of whichever side has fewer distinct ones among these candidates (many old
+  // poses against the newest one: one group, whichever way round the pairs were written)
+  std::map<int, std::vector<int64_t>> by_a, by_b;
+  for (int64_t q : off) {
+    by_a[c->h_pose_col[vab[(size_t)q]]].push_back(q);
+    by_b[c->h_pose_col[vab[(size_t)(n + q)]]].push_back(q);
+  }
+  const bool solve_a = by_a.size() < by_b.size();
+  std::map<int, std::vector<int64_t>> by_col;                     // slots of the device buffer, numbered group after group
+  std::vector<int> row_col;
+  for (const auto &grp : solve_a ? by_a : by_b) {
+    std::vector<int64_t> &slots = by_col[grp.first];
+    for (int64_t q : grp.second) {
+      const int64_t t = (int64_t)row_col.size();
+      slots.push_back(t);
+      row_col.push_back(c->h_pose_col[vab[(size_t)(solve_a ? n + q : q)]]);
+      // solved for b's columns: the slot holds rows a, columns b; for a's: rows b, columns a = Sigma_ab^T
+      enc[(size_t)(3 * q + 2)] = gate_extra_code(t, solve_a);
+    }
+  }
+  hipStream_t s = c->stream;
+  HIPCHK(c, G.d_extra.alloc(row_col.size() * 36));
+  HIPCHK(c, hipEventRecord(c->ev[0], s));
+  if ((rc = column_solves_resident(c, by_col, row_col, G.d_rhs, G.d_cols, G.d_extra.p)) != FGO_OK) return rc;
+  HIPCHK(c, hipEventRecord(c->ev[1], s));
+  G.n_off = (int64_t)off.size();
+  G.n_groups = (int64_t)by_col.size();
+  return FGO_OK;
+}
+
 // the record of one candidate / edge: inverse measurement (unit quaternion), information
 void gate_record(const double *meas7, const double *info21, double *rec) {
   const double *q = meas7 + 3;
@@ -422,60 +486,10 @@ int fgo_gate_edges_se3(fgo_ctx *c, int64_t n, const int64_t *id_a, const int64_t
   if (rc) return rc;
   if ((tangent_order == FGO_TANGENT_GTSAM) != c->gtsam_mode)
     return fail(c, FGO_EINVAL, "candidate edges must use the tangent order of the context's own semantics");
-  std::vector<int> idx;                                           // the free endpoints
-  for (int v : vab)
-    if (!c->fixed[v]) idx.push_back(v);
-  fgo_ctx::Gate &G = c->gate;
-  G.n_off = G.n_groups = 0;
-  G.ms_solves = 0;
   std::vector<int64_t> enc;
-  const bool with_cov = !idx.empty();                             // (every endpoint fixed: P = 0, no factorisation)
-  if (with_cov) {
-    if ((rc = ensure_columns(c, &idx)) != FGO_OK) return rc;
-    if ((rc = sigma_ready(c)) != FGO_OK) return rc;
-    if ((rc = host_pose_cols(c)) != FGO_OK) return rc;
-    const Symbolic &S = c->S;
-    enc.assign((size_t)(3 * n), GATE_ZERO);
-    std::vector<int64_t> off;                                     // candidates whose Sigma_ab is off the pattern of L
-    for (int64_t q = 0; q < n; ++q) {
-      const int va = vab[(size_t)q], vb = vab[(size_t)(n + q)];
-      const int ca = c->fixed[va] ? -1 : c->h_pose_col[va], cb = c->fixed[vb] ? -1 : c->h_pose_col[vb];
-      if (ca >= 0) enc[(size_t)(3 * q)] = S.colptr[ca] << 1;
-      if (cb >= 0) enc[(size_t)(3 * q + 1)] = S.colptr[cb] << 1;
-      if (ca < 0 || cb < 0) continue;
-      const int64_t code = pattern_code(S, ca, cb);
-      if (code >= 0) enc[(size_t)(3 * q + 2)] = code; else off.push_back(q);
-    }
-    if (!off.empty()) {
-      // Sigma_ab = Sigma_ba^T: solve for the columns of whichever side has fewer distinct ones among these candidates (many old
-      // poses against the newest one: one group, whichever way round the pairs were written)
-      std::map<int, std::vector<int64_t>> by_a, by_b;
-      for (int64_t q : off) {
-        by_a[c->h_pose_col[vab[(size_t)q]]].push_back(q);
-        by_b[c->h_pose_col[vab[(size_t)(n + q)]]].push_back(q);
-      }
-      const bool solve_a = by_a.size() < by_b.size();
-      std::map<int, std::vector<int64_t>> by_col;                 // slots of the device buffer, numbered group after group
-      std::vector<int> row_col;
-      for (const auto &grp : solve_a ? by_a : by_b) {
-        std::vector<int64_t> &slots = by_col[grp.first];
-        for (int64_t q : grp.second) {
-          const int64_t t = (int64_t)row_col.size();
-          slots.push_back(t);
-          row_col.push_back(c->h_pose_col[vab[(size_t)(solve_a ? n + q : q)]]);
-          // solved for b's columns: the slot holds rows a, columns b; for a's: rows b, columns a = Sigma_ab^T
-          enc[(size_t)(3 * q + 2)] = gate_extra_code(t, solve_a);
-        }
-      }
-      hipStream_t s = c->stream;
-      HIPCHK(c, G.d_extra.alloc(row_col.size() * 36));
-      HIPCHK(c, hipEventRecord(c->ev[0], s));
-      if ((rc = column_solves_resident(c, by_col, row_col, G.d_rhs, G.d_cols, G.d_extra.p)) != FGO_OK) return rc;
-      HIPCHK(c, hipEventRecord(c->ev[1], s));
-      G.n_off = (int64_t)off.size();
-      G.n_groups = (int64_t)by_col.size();
-    }
-  }
+  bool with_cov = false;
+  if ((rc = gate_blocks(c, n, vab, enc, with_cov)) != FGO_OK) return rc;
+  fgo_ctx::Gate &G = c->gate;
   std::vector<double> rec((size_t)n * GATE_REC), out;
   for (int64_t q = 0; q < n; ++q) gate_record(meas7 + 7 * q, info_ut21 + 21 * q, &rec[(size_t)q * GATE_REC]);
   if ((rc = run_gate(c, n, vab, rec, enc, with_cov, with_cov && pred_cov36_out, out)) != FGO_OK) return rc;
@@ -531,5 +545,170 @@ int fgo_debug_gate_stats(const fgo_ctx *c, double out[4]) {
   out[3] = c->gate.ms_solves;
   return FGO_OK;
 }
+
+}  // extern "C"
+
+namespace {
+
+// one candidate plane observation: pose and plane variable, record.  Checks follow fgo_add_plane_factor (same normalisation of z)
+int plane_gate_stage(fgo_ctx *c, const std::string &at, int64_t pose_id, int64_t plane_id, const double *z, const double *cov6, int &vx, int &vp,
+                     double *rec) {
+  const auto x = c->id2idx.find(pose_id), p = c->id2idx.find(plane_id);
+  if (x == c->id2idx.end() || p == c->id2idx.end()) return fail(c, FGO_EINVAL, at + "unknown variable id");
+  if (c->var_kind[x->second] != 0) return fail(c, FGO_EINVAL, at + "the first variable of a plane observation is a pose");
+  if (c->var_kind[p->second] != 1) return fail(c, FGO_EINVAL, at + "the second variable of a plane observation is a plane");
+  vx = x->second; vp = p->second;
+  if (!z) return FGO_OK;
+  const double n = std::sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]);
+  if (!(n > 0)) return fail(c, FGO_EINVAL, at + "zero plane normal");
+  rec[0] = z[0] / n; rec[1] = z[1] / n; rec[2] = z[2] / n; rec[3] = z[3];
+  std::memcpy(rec + 4, cov6, 6 * sizeof(double));
+  return FGO_OK;
+}
+
+// the plane gate's single launch over n staged candidates (vxp: pose variable of every candidate, then plane variable); the output
+// stays in gate.d_out.  Timed between ev[2] and the caller's ev[3]
+int launch_plane_request(fgo_ctx *c, int64_t n, const std::vector<int> &vxp, const std::vector<double> &rec, const std::vector<int64_t> &enc, bool want_P) {
+  hipStream_t s = c->stream;
+  fgo_ctx::Gate &G = c->gate;
+  HIPCHK(c, G.d_v.upload(vxp, s));
+  HIPCHK(c, G.d_rec.upload(rec, s));
+  HIPCHK(c, G.d_enc.upload(enc, s));
+  HIPCHK(c, G.d_out.alloc((size_t)n * (want_P ? 16 : 7)));
+  PlaneGatePlan A{};
+  A.n = n;
+  A.vx = G.d_v.p; A.vp = G.d_v.p + n;
+  A.rec = G.d_rec.p;
+  A.enc = G.d_enc.p;
+  A.Sig = c->sinv.d_Sig.p; A.extra = G.d_extra.p;
+  A.out = G.d_out.p;
+  A.want_P = want_P ? 1 : 0;
+  HIPCHK(c, hipEventRecord(c->ev[2], s));
+  launch_plane_gate(A, c->d_poses[c->cur].p, s);
+  return FGO_OK;
+}
+
+// after the request's synchronisation: the device times of its kernels and of the column solves
+int plane_gate_times(fgo_ctx *c) {
+  fgo_ctx::Gate &G = c->gate;
+  float ms = 0;
+  HIPCHK(c, hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+  G.ms_kernel = ms;
+  if (G.n_groups > 0) {
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    G.ms_solves = ms;
+  }
+  return FGO_OK;
+}
+
+int plane_gate_checks(fgo_ctx *c) {
+  const int rc = common_checks(c);
+  if (rc) return rc;
+  if (!c->gtsam_mode) return fail(c, FGO_EINVAL, "plane observations need a GTSAM-semantics context");
+  return FGO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fgo_gate_plane_factors(fgo_ctx *c, int64_t n, const int64_t *pose_id, const int64_t *plane_id, const double *z_abcd, const double *cov_ut6,
+                           double *d2_out, double *chi2_out, double *cos_out, double *resid3_out, double *pred_cov9_out) try {
+  if (!c || n < 0) return FGO_EINVAL;
+  if (n == 0) return FGO_OK;
+  if (!pose_id || !plane_id || !z_abcd || !cov_ut6 || !d2_out) return FGO_EINVAL;
+  const auto at = [](int64_t q) { return "candidate " + std::to_string(q) + ": "; };
+  std::vector<int> vxp((size_t)(2 * n));
+  std::vector<double> rec((size_t)n * PGATE_REC);
+  int rc;
+  for (int64_t q = 0; q < n; ++q)
+    if ((rc = plane_gate_stage(c, at(q), pose_id[q], plane_id[q], z_abcd + 4 * q, cov_ut6 + 6 * q, vxp[(size_t)q], vxp[(size_t)(n + q)],
+                               &rec[(size_t)q * PGATE_REC])) != FGO_OK)
+      return rc;
+  if ((rc = plane_gate_checks(c)) != FGO_OK) return rc;
+  std::vector<int64_t> enc;
+  bool with_cov = false;
+  if ((rc = gate_blocks(c, n, vxp, enc, with_cov)) != FGO_OK) return rc;
+  if (!with_cov) enc.assign((size_t)(3 * n), GATE_ZERO);
+  const bool want_P = pred_cov9_out != nullptr;
+  if ((rc = launch_plane_request(c, n, vxp, rec, enc, want_P)) != FGO_OK) return rc;
+  hipStream_t s = c->stream;
+  std::vector<double> out((size_t)n * (want_P ? 16 : 7));
+  HIPCHK(c, hipEventRecord(c->ev[3], s));
+  HIPCHK(c, hipMemcpyAsync(out.data(), c->gate.d_out.p, sizeof(double) * out.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  if ((rc = plane_gate_times(c)) != FGO_OK) return rc;
+  for (int64_t q = 0; q < n; ++q) {
+    const double st = out[(size_t)(3 * n + q)];
+    if (st == 1.0) return fail(c, FGO_ENUM, at(q) + "measurement covariance not positive definite");
+    if (st != 0.0) return fail(c, FGO_ENUM, at(q) + "innovation covariance not positive definite");
+  }
+  std::memcpy(d2_out, out.data(), sizeof(double) * (size_t)n);
+  if (chi2_out) std::memcpy(chi2_out, out.data() + n, sizeof(double) * (size_t)n);
+  if (cos_out) std::memcpy(cos_out, out.data() + 2 * n, sizeof(double) * (size_t)n);
+  if (resid3_out) std::memcpy(resid3_out, out.data() + 4 * n, sizeof(double) * 3 * (size_t)n);
+  if (pred_cov9_out) std::memcpy(pred_cov9_out, out.data() + 7 * n, sizeof(double) * 9 * (size_t)n);
+  return FGO_OK;
+} FGO_CATCH_INT(c)
+
+int fgo_associate_planes(fgo_ctx *c, int64_t pose_id, int64_t k, const double *z_abcd, const double *cov_ut6, int64_t m, const int64_t *plane_ids,
+                         double d2_gate, double cos_min, int64_t *match_out, double *best2_out, double *d2_matrix_out) try {
+  if (!c || k < 0 || m < 0) return FGO_EINVAL;
+  if (k == 0) return FGO_OK;
+  if (!z_abcd || !cov_ut6 || !match_out || !best2_out || (m > 0 && !plane_ids)) return FGO_EINVAL;
+  if (m == 0) {
+    for (int64_t i = 0; i < k; ++i) { match_out[i] = -1; best2_out[2 * i] = best2_out[2 * i + 1] = HUGE_VAL; }
+    return FGO_OK;
+  }
+  // the m pairs (pose, plane j) first: the k observations of a pair share its three covariance blocks
+  std::vector<int> pair_v((size_t)(2 * m));
+  std::set<int64_t> seen;
+  int rc;
+  for (int64_t j = 0; j < m; ++j) {
+    const std::string at = "plane " + std::to_string(j) + ": ";
+    if ((rc = plane_gate_stage(c, at, pose_id, plane_ids[j], nullptr, nullptr, pair_v[(size_t)j], pair_v[(size_t)(m + j)], nullptr)) != FGO_OK) return rc;
+    if (!seen.insert(plane_ids[j]).second) return fail(c, FGO_EINVAL, at + "listed twice");
+  }
+  const int64_t n = k * m;
+  std::vector<double> rec((size_t)n * PGATE_REC);
+  for (int64_t i = 0; i < k; ++i) {                                // candidate j k + i = observation i against plane j
+    int vx, vp;
+    double *r0 = &rec[(size_t)i * PGATE_REC];
+    if ((rc = plane_gate_stage(c, "observation " + std::to_string(i) + ": ", pose_id, plane_ids[0], z_abcd + 4 * i, cov_ut6 + 6 * i, vx, vp, r0)) != FGO_OK)
+      return rc;
+    for (int64_t j = 1; j < m; ++j) std::memcpy(&rec[(size_t)(j * k + i) * PGATE_REC], r0, PGATE_REC * sizeof(double));
+  }
+  if ((rc = plane_gate_checks(c)) != FGO_OK) return rc;
+  std::vector<int64_t> pair_enc;
+  bool with_cov = false;
+  if ((rc = gate_blocks(c, m, pair_v, pair_enc, with_cov)) != FGO_OK) return rc;
+  if (!with_cov) pair_enc.assign((size_t)(3 * m), GATE_ZERO);
+  fgo_ctx::Gate &G = c->gate;
+  G.n_off *= k;                                                    // (candidates, not pairs)
+  std::vector<int> vxp((size_t)(2 * n));
+  std::vector<int64_t> enc((size_t)(3 * n));
+  for (int64_t j = 0; j < m; ++j)
+    for (int64_t i = 0; i < k; ++i) {
+      const int64_t q = j * k + i;
+      vxp[(size_t)q] = pair_v[(size_t)j]; vxp[(size_t)(n + q)] = pair_v[(size_t)(m + j)];
+      for (int t = 0; t < 3; ++t) enc[(size_t)(3 * q + t)] = pair_enc[(size_t)(3 * j + t)];
+    }
+  if ((rc = launch_plane_request(c, n, vxp, rec, enc, false)) != FGO_OK) return rc;
+  hipStream_t s = c->stream;
+  const bool want_matrix = d2_matrix_out != nullptr;
+  std::vector<double> res((size_t)(3 * k + (want_matrix ? n : 0)));
+  HIPCHK(c, G.d_res.alloc(res.size()));
+  launch_plane_assoc(G.d_out.p, k, m, d2_gate, cos_min, want_matrix, G.d_res.p, s);
+  HIPCHK(c, hipEventRecord(c->ev[3], s));
+  HIPCHK(c, hipMemcpyAsync(res.data(), G.d_res.p, sizeof(double) * res.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  if ((rc = plane_gate_times(c)) != FGO_OK) return rc;
+  for (int64_t i = 0; i < k; ++i) match_out[i] = res[(size_t)i] < 0 ? -1 : plane_ids[(int64_t)res[(size_t)i]];
+  std::memcpy(best2_out, res.data() + k, sizeof(double) * 2 * (size_t)k);
+  if (want_matrix) std::memcpy(d2_matrix_out, res.data() + 3 * k, sizeof(double) * (size_t)n);
+  return FGO_OK;
+} FGO_CATCH_INT(c)
 
 }  // extern "C"

@@ -232,7 +232,7 @@ double fgo_error(fgo_ctx *ctx);
  *      (J' Omega J)^-1 at the current estimate.  Works for both semantics. */
 int fgo_marginal_cov(fgo_ctx *ctx, int64_t id, double *cov36);
 /* Several blocks from ONE factorisation (the reference asks for many per Marginals object: gtsam/gtsam_graph.cpp:598-601,
- * :1357 + the commented-out association test :1413-1414): cov36 = n x 36 doubles.  The undamped factor stays resident in
+ * :1357 + the commented-out association test :1429-1476): cov36 = n x 36 doubles.  The undamped factor stays resident in
  * HBM until the estimate or the structure changes, so consecutive calls do not re-factor either. */
 int fgo_marginal_cov_many(fgo_ctx *ctx, int64_t n, const int64_t *ids, double *cov36);
 /* SparseOptimizer::computeMarginals / Marginals for the whole map: the H^-1 diagonal blocks of EVERY free variable from one
@@ -256,7 +256,8 @@ int fgo_debug_selinv_stats(const fgo_ctx *ctx, double out[7]);
  *      utils::chi2(N, 0.95) against an ad-hoc rotation-only information matrix (gtsam/test_vro_imu_graph.cpp:679-778); plane
  *      association builds a Marginals object and then has the J Sigma J' test commented out in favour of fixed thresholds
  *      (gtsam/gtsam_graph.cpp:1357-1470); a commented-out robust kernel is the only defence against a bad loop closure
- *      (g2o/g2o_graph.cpp:130).  Here the exact test is one call.  For a candidate between a and b with measurement Z and
+ *      (g2o/g2o_graph.cpp:130).  Here the exact test is one call (fgo_gate_edges_se3 for pose-pose edges, fgo_gate_plane_factors /
+ *      fgo_associate_planes below for plane observations).  For a candidate between a and b with measurement Z and
  *      information Omega (positive definite), at the current estimate: e, Ja, Jb as the linearisation computes them for a real
  *      edge of the context's semantics; chi2 = e' Omega e; P = [Ja Jb] Sigma_{ab,ab} [Ja Jb]' with Sigma = (J' Omega J)^-1 of
  *      the graph (the blocks fgo_marginal_cov_pairs returns; a fixed endpoint contributes zero blocks, both fixed: P = 0);
@@ -272,8 +273,39 @@ int fgo_gate_edges_se3(fgo_ctx *ctx, int64_t n, const int64_t *id_a, const int64
 /* e' Omega e of the SE3 edges already in the graph, [first, first + n) in the order they were added (g2o: edge->chi2()); needs no
  *      factorisation.  Single-GPU entry point like the gate. */
 int fgo_edge_chi2_se3(fgo_ctx *ctx, int64_t first, int64_t n, double *chi2_out);
-/* [0] candidates of the last gate call whose Sigma_ab was off the factor's pattern, [1] column groups solved for them,
- *      [2] device ms of the gate kernel, [3] device ms of those column solves */
+/* ---- the same test for a plane observation (GTSAM-semantics contexts): plane association is the one site where the reference
+ *      builds a Marginals object live (gtsam/gtsam_graph.cpp:1357, for every key frame that carries planes), and the test it then
+ *      has commented out (:1429-1476) drops the pose/plane cross-covariance, which accepts too much.  A candidate is a pose x, a
+ *      plane p that is already a variable, a measurement z = (a, b, c, d) in the pose frame and its 3x3 covariance S (upper
+ *      triangle), both taken exactly as fgo_add_plane_factor takes them (the normal of z is normalised, d is not touched).  At the
+ *      current estimate: e (3), Jx (3x6), Jp (3x3) as the linearisation computes them for a real OrientedPlane3Factor;
+ *      chi2 = e' S^-1 e; P = Jx Sxx Jx' + Jx Sxp Jp' + Jp Sxp' Jx' + Jp Spp Jp' with the blocks of Sigma fgo_marginal_cov_pairs
+ *      returns (of a plane's padded block only the leading 3x3 / 6x3 part is read; a fixed endpoint contributes zero blocks, both
+ *      fixed: P = 0, no factorisation); d2 = e' (P + S)^-1 e, chi-square with 3 degrees of freedom for a correct association,
+ *      0 <= d2 <= chi2; cos = n' . n_z, the cosine between the predicted and the measured normal.  Accept when
+ *      d2 < utils::chi2(3, 0.95) = 7.815.  Nothing is added to the graph; the context is left as fgo_marginal_cov_pairs on the
+ *      same id pairs leaves it.
+ * n candidates.  d2_out[n]; chi2_out[n], cos_out[n], resid3_out[n x 3] (e) and pred_cov9_out[n x 9] (P, row-major) may be NULL.
+ *      FGO_EINVAL: unknown id, pose_id not a pose, plane_id not a plane, zero normal, g2o-semantics context; FGO_ENUM: S (or
+ *      P + S) is not positive definite (fgo_last_error names the first such candidate); FGO_ESTATE in distributed mode. */
+int fgo_gate_plane_factors(fgo_ctx *ctx, int64_t n, const int64_t *pose_id, const int64_t *plane_id, const double *z_abcd,
+                           const double *cov_ut6, double *d2_out, double *chi2_out, double *cos_out, double *resid3_out,
+                           double *pred_cov9_out);
+/* The association loop of gtsam/gtsam_graph.cpp:1367-1479 as one call: k observations (z_abcd k x 4, cov_ut6 k x 6) made from
+ *      pose_id against the m distinct planes plane_ids; all k m candidates are evaluated on the device.  A candidate with
+ *      cos < cos_min (the reference's COSA < COS10, :1409; -1 disables it) or whose S or P + S is not positive definite is
+ *      excluded.  Per observation the smallest and the second smallest d2 are reduced on the device, going through plane_ids from
+ *      its first entry to its last; a tie goes to the earlier entry.  match_out[k] = the plane of the smallest d2 if that is
+ *      < d2_gate, else -1; best2_out[k x 2] = smallest, second smallest d2 (+inf when absent: the runner-up shows ambiguity);
+ *      d2_matrix_out[k x m] (may be NULL) = every d2, +inf where the candidate was excluded.  Observations are matched independently
+ *      of one another, as the reference does.  k = 0: nothing is written; m = 0: match -1, best2 +inf.  Errors as above, and
+ *      FGO_EINVAL for a plane listed twice. */
+int fgo_associate_planes(fgo_ctx *ctx, int64_t pose_id, int64_t k, const double *z_abcd, const double *cov_ut6, int64_t m,
+                         const int64_t *plane_ids, double d2_gate, double cos_min, int64_t *match_out, double *best2_out,
+                         double *d2_matrix_out);
+/* the last gate call of either kind: [0] its candidates whose cross-covariance block was off the factor's pattern, [1] column
+ *      groups solved for them, [2] device ms of the gate kernel (and the association's reduction), [3] device ms of those column
+ *      solves */
 int fgo_debug_gate_stats(const fgo_ctx *ctx, double out[4]);
 
 /* ---- solve: ONE SparseOptimizer::optimize(max_iters) call as issued by
