@@ -40,6 +40,20 @@ class FgoStats(C.Structure):
         return d
 
 
+class TwoViewParams(C.Structure):
+    """fgo_two_view_params"""
+    _fields_ = [("pose_prior_sigma", C.c_double), ("point_sigma", C.c_double), ("pixel_sigma", C.c_double),
+                ("max_iters", C.c_int), ("min_matches", C.c_int)]
+
+
+class TwoViewResult(C.Structure):
+    """fgo_two_view_result"""
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("trials", C.c_int),
+                ("error_initial", C.c_double), ("error_final", C.c_double), ("lambda_final", C.c_double)]
+
+
+FGO_TV_OK, FGO_TV_TOO_FEW, FGO_TV_NUM = 0, 1, 2
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)     # fgo_allreduce_fn
 
 
@@ -117,6 +131,10 @@ def _load():
     lib.fgo_set_fixed.argtypes = [C.c_void_p, C.c_int64, C.c_int]
     lib.fgo_preint_information.argtypes = [dp, dp]
     lib.fgo_preint_batch.argtypes = [C.c_int, C.c_int64, C.POINTER(C.c_int64), dp, dp, C.c_double, dp, dp, dp]
+    lib.fgo_two_view_params_default.restype = None
+    lib.fgo_two_view_params_default.argtypes = [C.POINTER(TwoViewParams)]
+    lib.fgo_two_view_ba_batch.argtypes = [C.c_int, C.c_int64, i64p, dp, dp, dp, dp, dp, dp, C.POINTER(TwoViewParams), dp, dp, dp, dp,
+                                          C.POINTER(TwoViewResult)]
     lib.fgo_add_vec3.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_bias.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_prior_vec3.argtypes = [C.c_void_p, C.c_int64, dp, C.c_double]
@@ -172,6 +190,55 @@ def preint_batch(sample_ptr, acc, gyro, dt, bias_hat=None, params=None, device=0
     rc = lib.fgo_preint_batch(device, n, _i64p(sp), _dp(a), _dp(w), dt, None if bh is None else _dp(bh), _dp(params), _dp(out))
     if rc < 0:
         raise FgoError("fgo_preint_batch failed: %d" % rc)
+    return out
+
+
+def two_view_params(**kw):
+    """fgo_two_view_params_default, with the given fields replaced"""
+    p = TwoViewParams()
+    lib.fgo_two_view_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(TwoViewParams._fields_):
+            raise TypeError("fgo_two_view_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def two_view_ba_batch(match_ptr, xyz, uv_i, uv_j, calib9, pose_j0=None, body_P_sensor=None, params=None, device=0):
+    """fgo_two_view_ba_batch: CGraphGT::bundleAdjust for every pair in one launch, one wave per pair.  Pair p owns the matches
+    [match_ptr[p], match_ptr[p + 1]) of xyz (M x 3, camera i), uv_i / uv_j (M x 2).  Returns a dict of arrays over the pairs:
+    pose_j, pose_i (n x 7), cov (n x 6 x 6, tangent [omega; v]), info (n x 21, upper triangle), status (FGO_TV_*), iterations,
+    trials, error_initial, error_final, lambda_final."""
+    mp = np.ascontiguousarray(match_ptr, np.int64)
+    n = len(mp) - 1
+    if n < 0:
+        raise FgoError("two_view_ba_batch: match_ptr needs n_pairs + 1 entries")
+    x = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+    a = np.ascontiguousarray(uv_i, np.float64).reshape(-1, 2); b = np.ascontiguousarray(uv_j, np.float64).reshape(-1, 2)
+    m = int(mp[-1])
+    if min(len(x), len(a), len(b)) < m:
+        raise FgoError("two_view_ba_batch: match_ptr names %d matches, the arrays hold fewer" % m)
+    c9 = np.ascontiguousarray(calib9, np.float64)
+    if c9.shape != (9,):
+        raise FgoError("two_view_ba_batch: calib9 = fx fy s u0 v0 k1 k2 p1 p2")
+    p0 = None if pose_j0 is None else np.ascontiguousarray(pose_j0, np.float64).reshape(-1, 7)
+    if p0 is not None and len(p0) != n:
+        raise FgoError("two_view_ba_batch: pose_j0 needs one pose per pair")
+    bps = None if body_P_sensor is None else np.ascontiguousarray(body_P_sensor, np.float64)
+    if bps is not None and bps.shape != (7,):
+        raise FgoError("two_view_ba_batch: body_P_sensor = t(3) q_xyzw(4)")
+    pose_j = np.zeros((n, 7)); pose_i = np.zeros((n, 7)); cov = np.zeros((n, 6, 6)); info = np.zeros((n, 21))
+    res = (TwoViewResult * max(n, 1))()
+    rc = lib.fgo_two_view_ba_batch(device, n, _i64p(mp), _dp(x), _dp(a), _dp(b), None if p0 is None else _dp(p0), _dp(c9),
+                                   None if bps is None else _dp(bps), None if params is None else C.byref(params),
+                                   _dp(pose_j), _dp(pose_i), _dp(cov), _dp(info), res)
+    if rc < 0:
+        raise FgoError("fgo_two_view_ba_batch failed: %d" % rc)
+    r = np.frombuffer(res, dtype=np.dtype([("status", "i4"), ("iterations", "i4"), ("trials", "i4"), ("_pad", "i4"), ("error_initial", "f8"),
+                                           ("error_final", "f8"), ("lambda_final", "f8")]), count=n)
+    out = {"pose_j": pose_j, "pose_i": pose_i, "cov": cov, "info": info}
+    for k in ("status", "iterations", "trials", "error_initial", "error_final", "lambda_final"):
+        out[k] = r[k].copy()
     return out
 
 

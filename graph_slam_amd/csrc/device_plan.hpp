@@ -20,6 +20,8 @@ struct CamCalib {
   double bps[7];        // body_P_sensor as t(3) q(4)
   double ad[36];        // AdjointMap(body_P_sensor^-1) = d compose(X, B) / d X, row-major
 };
+// fills K from fx fy s u0 v0 k1 k2 p1 p2 and body_P_sensor (t, q_xyzw; NULL = identity); false: zero quaternion (fgo_core.cpp)
+bool cam_calib_make(CamCalib &K, const double calib9[9], const double *body_P_sensor7);
 
 // one CombinedImuFactor's payload in HBM: 288 doubles (2304 B)
 struct ImuPayload {

@@ -30,6 +30,32 @@ void pose_inv7(const double *a, double *o) {
   o[0] = -rx; o[1] = -ry; o[2] = -rz; o[3] = qx; o[4] = qy; o[5] = qz; o[6] = qw;
 }
 
+// the device-side calibration record (also filled by the context-free fgo_two_view_ba_batch); false: zero quaternion
+bool cam_calib_make(CamCalib &K, const double calib9[9], const double *body_P_sensor7) {
+  K.fx = calib9[0]; K.fy = calib9[1]; K.s = calib9[2]; K.u0 = calib9[3]; K.v0 = calib9[4];
+  K.k1 = calib9[5]; K.k2 = calib9[6]; K.p1 = calib9[7]; K.p2 = calib9[8];
+  const double ident[7] = {0, 0, 0, 0, 0, 0, 1};
+  const double *b = body_P_sensor7 ? body_P_sensor7 : ident;
+  const double n = std::sqrt(b[3] * b[3] + b[4] * b[4] + b[5] * b[5] + b[6] * b[6]);
+  if (!(n > 0)) return false;
+  for (int k = 0; k < 3; ++k) K.bps[k] = b[k];
+  for (int k = 3; k < 7; ++k) K.bps[k] = b[k] / n;
+  // AdjointMap(B^-1) = [[R, 0], [[t]x R, R]] of B^-1
+  double bi[7];
+  pose_inv7(K.bps, bi);
+  const double x = bi[3], y = bi[4], z = bi[5], w = bi[6];
+  const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w), 2 * (x * y + z * w), 1 - 2 * (x * x + z * z),
+                       2 * (y * z - x * w), 2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)};
+  const double S[9] = {0, -bi[2], bi[1], bi[2], 0, -bi[0], -bi[1], bi[0], 0};
+  for (int k = 0; k < 36; ++k) K.ad[k] = 0;
+  for (int r = 0; r < 3; ++r)
+    for (int q = 0; q < 3; ++q) {
+      K.ad[r * 6 + q] = R[r * 3 + q]; K.ad[(3 + r) * 6 + 3 + q] = R[r * 3 + q];
+      K.ad[(3 + r) * 6 + q] = S[r * 3] * R[q] + S[r * 3 + 1] * R[3 + q] + S[r * 3 + 2] * R[6 + q];
+    }
+  return true;
+}
+
 int upload_poses(fgo_ctx *c) {
   const int64_t N = (int64_t)c->ids.size();
   std::vector<double> p8((size_t)N * 8, 0.0);
@@ -388,27 +414,8 @@ int fgo_add_plane_factor(fgo_ctx *c, int64_t pose_id, int64_t plane_id, const do
 int fgo_set_calib_ds2(fgo_ctx *c, double fx, double fy, double s, double u0, double v0, double k1, double k2, double p1,
                       double p2, const double body_P_sensor7[7]) try {
   if (!c) return FGO_EINVAL;
-  CamCalib &K = c->cam;
-  K.fx = fx; K.fy = fy; K.s = s; K.u0 = u0; K.v0 = v0; K.k1 = k1; K.k2 = k2; K.p1 = p1; K.p2 = p2;
-  const double ident[7] = {0, 0, 0, 0, 0, 0, 1};
-  const double *b = body_P_sensor7 ? body_P_sensor7 : ident;
-  const double n = std::sqrt(b[3] * b[3] + b[4] * b[4] + b[5] * b[5] + b[6] * b[6]);
-  if (!(n > 0)) return fail(c, FGO_EINVAL, "zero quaternion");
-  for (int k = 0; k < 3; ++k) K.bps[k] = b[k];
-  for (int k = 3; k < 7; ++k) K.bps[k] = b[k] / n;
-  // AdjointMap(B^-1) = [[R, 0], [[t]x R, R]] of B^-1
-  double bi[7];
-  pose_inv7(K.bps, bi);
-  const double x = bi[3], y = bi[4], z = bi[5], w = bi[6];
-  const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w), 2 * (x * y + z * w), 1 - 2 * (x * x + z * z),
-                       2 * (y * z - x * w), 2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)};
-  const double S[9] = {0, -bi[2], bi[1], bi[2], 0, -bi[0], -bi[1], bi[0], 0};
-  for (int k = 0; k < 36; ++k) K.ad[k] = 0;
-  for (int r = 0; r < 3; ++r)
-    for (int q = 0; q < 3; ++q) {
-      K.ad[r * 6 + q] = R[r * 3 + q]; K.ad[(3 + r) * 6 + 3 + q] = R[r * 3 + q];
-      K.ad[(3 + r) * 6 + q] = S[r * 3] * R[q] + S[r * 3 + 1] * R[3 + q] + S[r * 3 + 2] * R[6 + q];
-    }
+  const double calib9[9] = {fx, fy, s, u0, v0, k1, k2, p1, p2};
+  if (!cam_calib_make(c->cam, calib9, body_P_sensor7)) return fail(c, FGO_EINVAL, "zero quaternion");
   c->cam_set = true;
   c->structure_dirty = true;       // the calibration travels inside the device plan
   return FGO_OK;

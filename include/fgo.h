@@ -122,6 +122,46 @@ int fgo_add_reproj(fgo_ctx *ctx, int64_t pose_id, int64_t point_id, const double
 /* bulk forms: n points (+ PriorFactor<Point3> when prior_sigma > 0) / n projection factors */
 int fgo_add_points3(fgo_ctx *ctx, int64_t n, const int64_t *ids, const double *xyz, double prior_sigma);
 int fgo_add_reprojs(fgo_ctx *ctx, int64_t n, const int64_t *pose_ids, const int64_t *point_ids, const double *uv, double sigma);
+/* Batched two-view bundle adjustment: CGraphGT::bundleAdjust (gtsam/gtsam_graph.cpp:500-610) for n_pairs independent
+ * visual-odometry records in ONE launch, one wave per pair (the reference's offline tools call it record after record:
+ * gtsam/test/convert_vo2ba.cpp:210-243, :300, convert_vo2ba_2.cpp:177).  Pair p owns the matches
+ * [match_ptr[p], match_ptr[p+1]) of xyz_i (the feature in camera i, M x 3), uv_i / uv_j (its pixel in either image, M x 2):
+ *      pose i   starts at identity, PriorFactor<Pose3>(identity, sigma pose_prior_sigma)          :537
+ *      pose j   starts at pose_j0[p] (t(3) q_xyzw(4), unit quaternion; NULL = identity, as the reference starts), free
+ *      point k  starts at xyz_i[k], PriorFactor<Point3>(xyz_i[k], sigma point_sigma)              :574
+ *      two GenericProjectionFactor<Pose3, Point3, Cal3DS2>(sigma pixel_sigma) per match           :539
+ *      calib9 = fx fy s u0 v0 k1 k2 p1 p2 and body_P_sensor7 as fgo_set_calib_ds2 takes them (NULL = identity);
+ *      cheirality as in a context (throwCheirality = false).
+ * LevenbergMarquardtOptimizer::optimize() with the controller of fgo_optimize_gtsam (lambda0 1e-5, factor 10, upper bound
+ * 1e5, identity damping on poses and points, minModelFidelity 1e-3, relative / absolute tolerance 1e-5); then the system is
+ * linearised undamped at the final estimate: cov36_out = Marginals::marginalCovariance of pose j (6x6 row-major, tangent
+ * [omega; v]), info_ut21_out = its inverse, symmetric by construction, as the 21 upper-triangular entries
+ * fgo_add_edge_se3(..., FGO_TANGENT_GTSAM) takes.  error_* = 0.5 sum |whitened r|^2, priors included.
+ * Stateless, host arrays in and out, like fgo_preint_batch.  FGO_EINVAL (before any HIP call): negative or decreasing
+ * match_ptr, more than INT_MAX / 3 matches in one pair, a NULL required pointer, a sigma <= 0, min_matches < 3, a zero quaternion in body_P_sensor7; FGO_ENODEV without a
+ * HIP device (no CPU fallback).  n_pairs == 0: FGO_OK.  A numerical failure of one pair is that pair's status: the call still
+ * returns FGO_OK and no other pair is affected (a pair's result does not depend on what else is in the batch). */
+typedef struct {
+  double pose_prior_sigma;   /* 1e-7   gtsam_graph.cpp:537 */
+  double point_sigma;        /* 0.014  :574 */
+  double pixel_sigma;        /* 1.0    :539 */
+  int max_iters;             /* <= 0: 100 (GTSAM default) */
+  int min_matches;           /* 5: the reference returns false for matches.size() <= 4 (:513); values < 3 are FGO_EINVAL */
+} fgo_two_view_params;
+void fgo_two_view_params_default(fgo_two_view_params *p);
+#define FGO_TV_OK 0
+#define FGO_TV_TOO_FEW 1     /* fewer than min_matches: pose_j_out = start, cov / info zero */
+#define FGO_TV_NUM 2         /* a non-finite residual, or a pivot of the undamped reduced system <= 0 or non-finite:
+                                the pose is returned as LM left it, cov / info zero */
+typedef struct { int status, iterations, trials; double error_initial, error_final, lambda_final; } fgo_two_view_result;
+int fgo_two_view_ba_batch(int device, int64_t n_pairs, const int64_t *match_ptr /* n_pairs + 1 */,
+                          const double *xyz_i /* M x 3 */, const double *uv_i /* M x 2 */, const double *uv_j /* M x 2 */,
+                          const double *pose_j0 /* n_pairs x 7, NULL = identity */,
+                          const double calib9[9], const double body_P_sensor7[7] /* NULL = identity */,
+                          const fgo_two_view_params *params /* NULL = defaults */,
+                          double *pose_j_out /* n x 7 */, double *pose_i_out /* n x 7, may be NULL */,
+                          double *cov36_out /* n x 36, may be NULL */, double *info_ut21_out /* n x 21, may be NULL */,
+                          fgo_two_view_result *result /* n */);
 /* ---- IMU: velocity / bias variables, their priors, preintegration and the CombinedImuFactor.
  *      Values::insert(V(id), Vector3) / insert(B(id), imuBias::ConstantBias) + PriorFactor<Vector3>(Isotropic::Sigma(3,
  *      1e-3)) / PriorFactor<ConstantBias>(Isotropic::Sigma(6, 1e-3)) — gtsam/gtsam_graph.cpp:346-367.
