@@ -42,11 +42,14 @@ __device__ __forceinline__ V3 unit3_retract(V3 n, double v0, double v1) {
 }
 __device__ __forceinline__ void unit3_local(V3 n, V3 y, double v[2]) {
   const double x = dot3(n, y);
-  if (x > 1.0 - 1e-16) { v[0] = v[1] = 0; return; }
-  if (x < -1.0 + 1e-16) { v[0] = 3.14159265358979323846; v[1] = 0; return; }
-  const double th = acos(x), k = th / sin(th);
+  // the angle from the component of y orthogonal to n (atan2), not from acos(x), which is flat at x = 1
+  const V3 o = {y.x - x * n.x, y.y - x * n.y, y.z - x * n.z};
+  const double s = sqrt(dot3(o, o));
+  // below the rounding of two unit vectors (|o| itself carries ~4e-16) y is n, or its antipode: [pi, 0] by convention
+  if (s < 1e-15) { v[0] = x > 0 ? 0 : 3.14159265358979323846; v[1] = 0; return; }
+  const double k = atan2(s, x) / s;
   const Basis B = unit3_basis(n);
-  const V3 h = {k * (y.x - x * n.x), k * (y.y - x * n.y), k * (y.z - x * n.z)};
+  const V3 h = {k * o.x, k * o.y, k * o.z};
   v[0] = dot3(B.b1, h); v[1] = dot3(B.b2, h);
 }
 

@@ -15,8 +15,7 @@ __device__ __forceinline__ M3 so3_dexp(V3 w) {
   const double th2 = dot3(w, w), th = sqrt(th2);
   const M3 W = skew(w), W2 = mm(W, W);
   double a, b;
-  if (th < 1e-5) { a = 0.5 - th2 / 24.0; b = 1.0 / 6.0 - th2 / 120.0; }
-  else { a = (1 - cos(th)) / th2; b = (th - sin(th)) / (th2 * th); }
+  so3_ab(th2, th, a, b);
   M3 J;
 #pragma unroll
   for (int k = 0; k < 9; ++k) J.m[k] = -a * W.m[k] + b * W2.m[k];

@@ -50,7 +50,11 @@ Mat3 right_jacobian(const double w[3]) {
   const double t2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], t = std::sqrt(t2);
   const Mat3 W = hat(w), W2 = mul(W, W);
   double a, b;
-  if (t < 1e-5) { a = 0.5 - t2 / 24.0; b = 1.0 / 6.0 - t2 / 120.0; } else { a = (1 - std::cos(t)) / t2; b = (t - std::sin(t)) / (t2 * t); }
+  // series below 0.25, where the closed forms lose eps / t^2 to cancellation (the same switch as pose3_device.hpp's so3_ab)
+  if (t < 0.25) {
+    a = 0.5 - t2 * (1.0 / 24.0 - t2 * (1.0 / 720.0 - t2 * (1.0 / 40320.0 - t2 / 3628800.0)));
+    b = 1.0 / 6.0 - t2 * (1.0 / 120.0 - t2 * (1.0 / 5040.0 - t2 * (1.0 / 362880.0 - t2 / 39916800.0)));
+  } else { a = (1 - std::cos(t)) / t2; b = (t - std::sin(t)) / (t2 * t); }
   Mat3 J;
   for (int k = 0; k < 9; ++k) J.a[k] = -a * W.a[k] + b * W2.a[k];
   J(0, 0) += 1; J(1, 1) += 1; J(2, 2) += 1;

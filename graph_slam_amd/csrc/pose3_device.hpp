@@ -32,6 +32,25 @@ __device__ __forceinline__ Pose pose_inv(const Pose &a) {
   c.t = {-r.x, -r.y, -r.z};
   return c;
 }
+// Small-angle coefficients.  Every closed form below divides a difference of O(th^k) terms by th^k and so loses eps / th^k
+// to cancellation; below kSeriesBelow the Maclaurin series (five terms: truncation th^10 / 5e8 or less, under 2e-15 at the
+// switch) is used instead.  The switch sits where the two errors meet; above it the closed forms are evaluated as before.
+constexpr double kSeriesBelow = 0.25;
+// a = (1 - cos th) / th^2,  b = (th - sin th) / th^3:  Expmap's V = I + a W + b W^2, right Jacobian I - a W + b W^2
+__device__ __forceinline__ void so3_ab(double th2, double th, double &a, double &b) {
+  if (th < kSeriesBelow) {
+    a = 0.5 - th2 * (1.0 / 24.0 - th2 * (1.0 / 720.0 - th2 * (1.0 / 40320.0 - th2 / 3628800.0)));
+    b = 1.0 / 6.0 - th2 * (1.0 / 120.0 - th2 * (1.0 / 5040.0 - th2 * (1.0 / 362880.0 - th2 / 39916800.0)));
+  } else {
+    a = (1 - cos(th)) / th2;
+    b = (th - sin(th)) / (th2 * th);
+  }
+}
+// c = 1/th^2 - (1 + cos th) / (2 th sin th):  inverse right Jacobian I + W/2 + c W^2
+__device__ __forceinline__ double so3_c(double th2, double th) {
+  if (th < kSeriesBelow) return 1.0 / 12.0 + th2 * (1.0 / 720.0 + th2 * (1.0 / 30240.0 + th2 * (1.0 / 1209600.0 + th2 / 47900160.0)));
+  return 1.0 / th2 - (1.0 + cos(th)) / (2.0 * th * sin(th));
+}
 // Rot3::Expmap as a unit quaternion
 __device__ __forceinline__ Q4 so3_exp(V3 w) {
   const double th2 = dot3(w, w), th = sqrt(th2);
@@ -49,7 +68,7 @@ __device__ __forceinline__ V3 so3_log(Q4 q) {
 __device__ __forceinline__ M3 so3_dlog(V3 w) {
   const double th2 = dot3(w, w), th = sqrt(th2);
   const M3 W = skew(w), W2 = mm(W, W);
-  const double c = th < 1e-5 ? 1.0 / 12.0 + th2 / 720.0 : 1.0 / th2 - (1.0 + cos(th)) / (2.0 * th * sin(th));
+  const double c = so3_c(th2, th);
   M3 J;
 #pragma unroll
   for (int k = 0; k < 9; ++k) J.m[k] = 0.5 * W.m[k] + c * W2.m[k];
@@ -62,11 +81,11 @@ __device__ __forceinline__ Pose se3_exp(const double xi[6]) {
   Pose T;
   T.q = so3_exp(w);
   const double th2 = dot3(w, w);
-  if (th2 < 1e-20) { T.t = v; return T; }
-  const V3 c = cross(w, v);
-  const V3 Rc = mv(qmat(T.q), c);
-  const double wv = dot3(w, v);
-  T.t = {(c.x - Rc.x + w.x * wv) / th2, (c.y - Rc.y + w.y * wv) / th2, (c.z - Rc.z + w.z * wv) / th2};
+  double a, b;
+  so3_ab(th2, sqrt(th2), a, b);
+  // t = (I + a W + b W^2) v: no difference of O(1) vectors divided by th^2, so accurate down to th = 0
+  const V3 c = cross(w, v), cc = cross(w, c);
+  T.t = {v.x + a * c.x + b * cc.x, v.y + a * c.y + b * cc.y, v.z + a * c.z + b * cc.z};
   return T;
 }
 // Pose3::Logmap -> xi[6] = [omega; u]
@@ -74,7 +93,14 @@ __device__ __forceinline__ void se3_log(const Pose &T, double xi[6]) {
   const V3 w = so3_log(T.q);
   const double th = sqrt(dot3(w, w));
   xi[0] = w.x; xi[1] = w.y; xi[2] = w.z;
-  if (th < 1e-10) { xi[3] = T.t.x; xi[4] = T.t.y; xi[5] = T.t.z; return; }
+  if (th < kSeriesBelow) {              // u = (I - W/2 + c W^2) t with the series c, down to th = 0
+    const double c = so3_c(th * th, th);
+    const V3 Wt = cross(w, T.t), WWt = cross(w, Wt);
+    xi[3] = T.t.x - 0.5 * Wt.x + c * WWt.x;
+    xi[4] = T.t.y - 0.5 * Wt.y + c * WWt.y;
+    xi[5] = T.t.z - 0.5 * Wt.z + c * WWt.z;
+    return;
+  }
   const V3 a = {w.x / th, w.y / th, w.z / th};
   const V3 Wt = cross(a, T.t), WWt = cross(a, Wt);
   const double k = 1.0 - th / (2.0 * tan(0.5 * th));
@@ -98,13 +124,16 @@ __device__ __forceinline__ M6 se3_dlog(const double xi[6]) {
   const M3 WV = mm(W, V), VW = mm(V, W), WVW = mm(WV, W), WW = mm(W, W), WWV = mm(WW, V), VWW = mm(VW, W);
   const M3 WVWW = mm(WVW, W), WWVW = mm(W, WVW);
   double c1, c2, c3;
-  if (ph > 1e-5) {
+  if (ph >= kSeriesBelow) {
     const double s = sin(ph), c = cos(ph), ph3 = ph2 * ph, ph4 = ph2 * ph2, ph5 = ph4 * ph;
     c1 = (ph - s) / ph3;
     c2 = (1 - ph2 / 2 - c) / ph4;
     c3 = -0.5 * ((1 - ph2 / 2 - c) / ph4 - 3 * (ph - s - ph3 / 6.) / ph5);
-  } else {
-    c1 = 1. / 6.; c2 = 1. / 24.; c3 = -0.5 * (1. / 24. + 3. / 120.);
+  } else {                               // limits -1/24 and +1/120: the series of the closed forms above
+    c1 = 1.0 / 6.0 - ph2 * (1.0 / 120.0 - ph2 * (1.0 / 5040.0 - ph2 * (1.0 / 362880.0 - ph2 / 39916800.0)));
+    c2 = -1.0 / 24.0 + ph2 * (1.0 / 720.0 - ph2 * (1.0 / 40320.0 - ph2 * (1.0 / 3628800.0 - ph2 / 479001600.0)));
+    const double d = -1.0 / 120.0 + ph2 * (1.0 / 5040.0 - ph2 * (1.0 / 362880.0 - ph2 * (1.0 / 39916800.0 - ph2 / 6227020800.0)));   // (ph - sin ph - ph^3/6) / ph^5
+    c3 = -0.5 * (c2 - 3 * d);
   }
   M3 Q;
 #pragma unroll

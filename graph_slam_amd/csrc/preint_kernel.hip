@@ -54,7 +54,11 @@ __device__ __forceinline__ M3 right_jacobian(const double w[3]) {
   const double t2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], t = sqrt(t2);
   const M3 W = hat3(w), W2 = mul3(W, W);
   double a, b;
-  if (t < 1e-5) { a = 0.5 - t2 / 24.0; b = 1.0 / 6.0 - t2 / 120.0; } else { a = (1 - cos(t)) / t2; b = (t - sin(t)) / (t2 * t); }
+  // series below 0.25, where the closed forms lose eps / t^2 to cancellation (the same switch as pose3_device.hpp's so3_ab)
+  if (t < 0.25) {
+    a = 0.5 - t2 * (1.0 / 24.0 - t2 * (1.0 / 720.0 - t2 * (1.0 / 40320.0 - t2 / 3628800.0)));
+    b = 1.0 / 6.0 - t2 * (1.0 / 120.0 - t2 * (1.0 / 5040.0 - t2 * (1.0 / 362880.0 - t2 / 39916800.0)));
+  } else { a = (1 - cos(t)) / t2; b = (t - sin(t)) / (t2 * t); }
   M3 J;
 #pragma unroll
   for (int k = 0; k < 9; ++k) J.a[k] = -a * W.a[k] + b * W2.a[k];

@@ -57,8 +57,7 @@ static inline void orc_so3_dexp(const double w[3], double J[9]) {
   orc_skew(w, W);
   orc_m3mul(W, W, W2);
   double a, b;
-  if (th < 1e-5) { a = 0.5 - th2 / 24.0; b = 1.0 / 6.0 - th2 / 120.0; }
-  else { a = (1 - cos(th)) / th2; b = (th - sin(th)) / (th2 * th); }
+  orc_so3_ab(th2, th, &a, &b);
   for (int k = 0; k < 9; ++k) J[k] = -a * W[k] + b * W2[k];
   J[0] += 1; J[4] += 1; J[8] += 1;
 }

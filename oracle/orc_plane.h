@@ -42,13 +42,15 @@ static inline void orc_unit3_retract(const double n[3], const double v[2], doubl
 /* Unit3::localCoordinates */
 static inline void orc_unit3_local(const double n[3], const double y[3], double v[2]) {
   const double x = n[0] * y[0] + n[1] * y[1] + n[2] * y[2];
-  if (x > 1.0 - 1e-16) { v[0] = v[1] = 0; return; }
-  if (x < -1.0 + 1e-16) { v[0] = M_PI; v[1] = 0; return; }
-  const double th = acos(x), k = th / sin(th);
+  /* the angle from the component of y orthogonal to n (atan2), not from acos(x), which is flat at x = 1 */
+  double h[3] = {y[0] - x * n[0], y[1] - x * n[1], y[2] - x * n[2]};
+  const double s = sqrt(h[0] * h[0] + h[1] * h[1] + h[2] * h[2]);
+  /* below the rounding of two unit vectors (|h| itself carries ~4e-16) y is n, or its antipode: [pi, 0] by convention */
+  if (s < 1e-15) { v[0] = x > 0 ? 0 : M_PI; v[1] = 0; return; }
+  const double k = atan2(s, x) / s;
   double B[6];
   orc_unit3_basis(n, B);
-  double h[3];
-  for (int i = 0; i < 3; ++i) h[i] = k * (y[i] - x * n[i]);
+  for (int i = 0; i < 3; ++i) h[i] *= k;
   v[0] = B[0] * h[0] + B[2] * h[1] + B[4] * h[2];
   v[1] = B[1] * h[0] + B[3] * h[1] + B[5] * h[2];
 }

@@ -21,6 +21,26 @@ static inline void orc_m3mul(const double A[9], const double B[9], double C[9]) 
   for (int r = 0; r < 3; ++r)
     for (int c = 0; c < 3; ++c) C[r * 3 + c] = A[r * 3] * B[c] + A[r * 3 + 1] * B[3 + c] + A[r * 3 + 2] * B[6 + c];
 }
+/* Small-angle coefficients.  Every closed form below divides a difference of O(th^k) terms by th^k and so loses
+ * eps / th^k to cancellation; below ORC_SERIES_BELOW the Maclaurin series (five terms: truncation th^10 / 5e8 or less,
+ * i.e. under 2e-15 at the switch) is used instead.  The switch sits where the two errors meet.  Above it the closed
+ * forms are evaluated exactly as before. */
+#define ORC_SERIES_BELOW 0.25
+/* a = (1 - cos th) / th^2,  b = (th - sin th) / th^3:  Expmap's V = I + a W + b W^2, right Jacobian I - a W + b W^2 */
+static inline void orc_so3_ab(double th2, double th, double *a, double *b) {
+  if (th < ORC_SERIES_BELOW) {
+    *a = 0.5 - th2 * (1.0 / 24.0 - th2 * (1.0 / 720.0 - th2 * (1.0 / 40320.0 - th2 / 3628800.0)));
+    *b = 1.0 / 6.0 - th2 * (1.0 / 120.0 - th2 * (1.0 / 5040.0 - th2 * (1.0 / 362880.0 - th2 / 39916800.0)));
+  } else {
+    *a = (1 - cos(th)) / th2;
+    *b = (th - sin(th)) / (th2 * th);
+  }
+}
+/* c = 1/th^2 - (1 + cos th) / (2 th sin th):  inverse right Jacobian I + W/2 + c W^2 */
+static inline double orc_so3_c(double th2, double th) {
+  if (th < ORC_SERIES_BELOW) return 1.0 / 12.0 + th2 * (1.0 / 720.0 + th2 * (1.0 / 30240.0 + th2 * (1.0 / 1209600.0 + th2 / 47900160.0)));
+  return 1.0 / th2 - (1.0 + cos(th)) / (2.0 * th * sin(th));
+}
 /* Rot3::Expmap as a unit quaternion */
 static inline void orc_so3_exp(const double w[3], double q[4]) {
   const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = sqrt(th2);
@@ -43,8 +63,7 @@ static inline void orc_so3_dlog(const double w[3], double J[9]) {
   double W[9], W2[9];
   orc_skew(w, W);
   orc_m3mul(W, W, W2);
-  double c; /* 1/th^2 - (1+cos)/(2 th sin) */
-  if (th < 1e-5) c = 1.0 / 12.0 + th2 / 720.0; else c = 1.0 / th2 - (1.0 + cos(th)) / (2.0 * th * sin(th));
+  const double c = orc_so3_c(th2, th);
   for (int k = 0; k < 9; ++k) J[k] = 0.5 * W[k] + c * W2[k];
   J[0] += 1; J[4] += 1; J[8] += 1;
 }
@@ -53,12 +72,12 @@ static inline void orc_se3_exp(const double xi[6], double T[7]) {
   const double *w = xi, *v = xi + 3;
   orc_so3_exp(w, T + 3);
   const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-  if (th2 < 1e-20) { T[0] = v[0]; T[1] = v[1]; T[2] = v[2]; return; }
-  const double wv = w[0] * v[0] + w[1] * v[1] + w[2] * v[2];
+  double a, b;
+  orc_so3_ab(th2, sqrt(th2), &a, &b);
+  /* t = (I + a W + b W^2) v: no difference of O(1) vectors divided by th^2, so accurate down to th = 0 */
   const double c[3] = {w[1] * v[2] - w[2] * v[1], w[2] * v[0] - w[0] * v[2], w[0] * v[1] - w[1] * v[0]};   /* w x v */
-  double Rc[3];
-  orc_qrot(T + 3, c, Rc);
-  for (int k = 0; k < 3; ++k) T[k] = (c[k] - Rc[k] + w[k] * wv) / th2;
+  const double cc[3] = {w[1] * c[2] - w[2] * c[1], w[2] * c[0] - w[0] * c[2], w[0] * c[1] - w[1] * c[0]};   /* w x (w x v) */
+  for (int k = 0; k < 3; ++k) T[k] = v[k] + a * c[k] + b * cc[k];
 }
 /* Pose3::Logmap -> [w; u] */
 static inline void orc_se3_log(const double T[7], double xi[6]) {
@@ -66,9 +85,15 @@ static inline void orc_se3_log(const double T[7], double xi[6]) {
   orc_so3_log(T + 3, w);
   const double th = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
   xi[0] = w[0]; xi[1] = w[1]; xi[2] = w[2];
-  if (th < 1e-10) { xi[3] = T[0]; xi[4] = T[1]; xi[5] = T[2]; return; }
-  const double a[3] = {w[0] / th, w[1] / th, w[2] / th};
   const double *t = T;
+  if (th < ORC_SERIES_BELOW) {           /* u = (I - W/2 + c W^2) t with the series c, down to th = 0 */
+    const double c = orc_so3_c(th * th, th);
+    const double Wt[3] = {w[1] * t[2] - w[2] * t[1], w[2] * t[0] - w[0] * t[2], w[0] * t[1] - w[1] * t[0]};
+    const double WWt[3] = {w[1] * Wt[2] - w[2] * Wt[1], w[2] * Wt[0] - w[0] * Wt[2], w[0] * Wt[1] - w[1] * Wt[0]};
+    for (int i = 0; i < 3; ++i) xi[3 + i] = t[i] - 0.5 * Wt[i] + c * WWt[i];
+    return;
+  }
+  const double a[3] = {w[0] / th, w[1] / th, w[2] / th};
   const double Wt[3] = {a[1] * t[2] - a[2] * t[1], a[2] * t[0] - a[0] * t[2], a[0] * t[1] - a[1] * t[0]};
   const double WWt[3] = {a[1] * Wt[2] - a[2] * Wt[1], a[2] * Wt[0] - a[0] * Wt[2], a[0] * Wt[1] - a[1] * Wt[0]};
   const double k = 1.0 - th / (2.0 * tan(0.5 * th));
@@ -97,13 +122,16 @@ static inline void orc_se3_dlog(const double xi[6], double J[36]) {
   orc_m3mul(W, W, WW); orc_m3mul(WW, V, WWV); orc_m3mul(VW, W, VWW);
   orc_m3mul(WVW, W, WVWW); orc_m3mul(W, WVW, WWVW);
   double c1, c2, c3;
-  if (ph > 1e-5) {
+  if (ph >= ORC_SERIES_BELOW) {
     const double s = sin(ph), c = cos(ph), ph3 = ph2 * ph, ph4 = ph2 * ph2, ph5 = ph4 * ph;
     c1 = (ph - s) / ph3;
     c2 = (1 - ph2 / 2 - c) / ph4;
     c3 = -0.5 * ((1 - ph2 / 2 - c) / ph4 - 3 * (ph - s - ph3 / 6.) / ph5);
-  } else {
-    c1 = 1. / 6.; c2 = 1. / 24.; c3 = -0.5 * (1. / 24. + 3. / 120.);
+  } else {                               /* limits -1/24 and +1/120: the series of the closed forms above */
+    c1 = 1.0 / 6.0 - ph2 * (1.0 / 120.0 - ph2 * (1.0 / 5040.0 - ph2 * (1.0 / 362880.0 - ph2 / 39916800.0)));
+    c2 = -1.0 / 24.0 + ph2 * (1.0 / 720.0 - ph2 * (1.0 / 40320.0 - ph2 * (1.0 / 3628800.0 - ph2 / 479001600.0)));
+    const double d = -1.0 / 120.0 + ph2 * (1.0 / 5040.0 - ph2 * (1.0 / 362880.0 - ph2 * (1.0 / 39916800.0 - ph2 / 6227020800.0)));   /* (ph - sin ph - ph^3/6) / ph^5 */
+    c3 = -0.5 * (c2 - 3 * d);
   }
   double Q[9], T1[9], Q2[9];
   for (int k = 0; k < 9; ++k)

@@ -209,6 +209,14 @@ class Preint:
             v = np.ascontiguousarray(variances, np.float64)
             lib.orc_preint_run_params(self.buf.ctypes.data, _dp(bhat), len(acc), _dp(acc), _dp(gyro), C.c_double(dt), _dp(v))
 
+    @classmethod
+    def from_buf(cls, buf):
+        """a payload that was integrated elsewhere (fgo_preint_batch, fgo_preint_integrate: same layout)"""
+        self = cls.__new__(cls)
+        self.buf = np.ascontiguousarray(buf, np.float64).copy()
+        assert self.buf.size == lib.orc_preint_size() // 8
+        return self
+
     def __getattr__(self, name):
         o = 0
         for f, k in self.FIELDS:
