@@ -54,6 +54,20 @@ class TwoViewResult(C.Structure):
 
 FGO_TV_OK, FGO_TV_TOO_FEW, FGO_TV_NUM = 0, 1, 2
 
+
+class PlaneCheckParams(C.Structure):
+    """fgo_plane_check_params"""
+    _fields_ = [("cos_min", C.c_double), ("d_max", C.c_double), ("failed_info00", C.c_double)]
+
+
+class PlaneCheckResult(C.Structure):
+    """fgo_plane_check_result"""
+    _fields_ = [("status", C.c_int), ("n_matched", C.c_int), ("n_bad", C.c_int), ("best_i", C.c_int), ("best_j", C.c_int),
+                ("reserved", C.c_int), ("err", C.c_double), ("err_raw", C.c_double)]
+
+
+FGO_PC_OK, FGO_PC_SKIPPED, FGO_PC_NUM = 0, 1, 2
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)     # fgo_allreduce_fn
 
 
@@ -135,6 +149,10 @@ def _load():
     lib.fgo_two_view_params_default.argtypes = [C.POINTER(TwoViewParams)]
     lib.fgo_two_view_ba_batch.argtypes = [C.c_int, C.c_int64, i64p, dp, dp, dp, dp, dp, dp, C.POINTER(TwoViewParams), dp, dp, dp, dp,
                                           C.POINTER(TwoViewResult)]
+    lib.fgo_plane_check_params_default.restype = None
+    lib.fgo_plane_check_params_default.argtypes = [C.POINTER(PlaneCheckParams)]
+    lib.fgo_plane_check_vro_batch.argtypes = [C.c_int, C.c_int64, dp, dp, dp, i64p, dp, dp, i64p, dp, dp, C.POINTER(PlaneCheckParams),
+                                              C.POINTER(PlaneCheckResult), i64p, dp, dp, dp, dp, dp]
     lib.fgo_add_vec3.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_bias.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_prior_vec3.argtypes = [C.c_void_p, C.c_int64, dp, C.c_double]
@@ -238,6 +256,58 @@ def two_view_ba_batch(match_ptr, xyz, uv_i, uv_j, calib9, pose_j0=None, body_P_s
                                            ("error_final", "f8"), ("lambda_final", "f8")]), count=n)
     out = {"pose_j": pose_j, "pose_i": pose_i, "cov": cov, "info": info}
     for k in ("status", "iterations", "trials", "error_initial", "error_final", "lambda_final"):
+        out[k] = r[k].copy()
+    return out
+
+
+def plane_check_params(**kw):
+    """fgo_plane_check_params_default, with the given fields replaced"""
+    p = PlaneCheckParams()
+    lib.fgo_plane_check_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(PlaneCheckParams._fields_):
+            raise TypeError("fgo_plane_check_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def plane_check_vro_batch(pose_ij, pi_ptr, pi_abcd, pi_cov, pj_ptr, pj_abcd, pj_cov, info=None, cov=None, params=None, device=0):
+    """fgo_plane_check_vro_batch: the plane check of gtsam/test_plane_check_vo.cpp for every record in one launch, one wave per
+    record.  Record r has the pose pose_ij[r] (n x 7) of frame j in frame i with either info[r] (n x 21, what two_view_ba_batch
+    returns) or cov[r] (n x 6 x 6), and owns the planes [pi_ptr[r], pi_ptr[r + 1]) of pi_abcd (Mi x 4) / pi_cov (Mi x 4 x 4, CPlane::m_CP)
+    seen in frame i and likewise [pj_ptr[r], pj_ptr[r + 1]) of pj_abcd / pj_cov seen in frame j.  Returns a dict of arrays: over the
+    records status (FGO_PC_*), n_matched, n_bad, best_i, best_j, err, err_raw; over the planes i match (index within the record's
+    j-list or -1), d2, raw, pred_abcd (Mi x 4), pred_cov (Mi x 3 x 3), sdj."""
+    ps = np.ascontiguousarray(pose_ij, np.float64).reshape(-1, 7)
+    n = len(ps)
+    ip = np.ascontiguousarray(pi_ptr, np.int64); jp = np.ascontiguousarray(pj_ptr, np.int64)
+    if len(ip) != n + 1 or len(jp) != n + 1:
+        raise FgoError("plane_check_vro_batch: pi_ptr and pj_ptr need n_records + 1 entries")
+    planes = []
+    for name, ptr, abcd, c16 in (("pi", ip, pi_abcd, pi_cov), ("pj", jp, pj_abcd, pj_cov)):
+        a = np.ascontiguousarray(abcd, np.float64).reshape(-1, 4); c = np.ascontiguousarray(c16, np.float64).reshape(-1, 16)
+        if min(len(a), len(c)) < int(ptr[-1]):
+            raise FgoError("plane_check_vro_batch: %s_ptr names %d planes, the arrays hold fewer" % (name, int(ptr[-1])))
+        planes += [a, c]
+    if (info is None) == (cov is None):
+        raise FgoError("plane_check_vro_batch: exactly one of info (n x 21) and cov (n x 6 x 6)")
+    s = np.ascontiguousarray(info if cov is None else cov, np.float64).reshape(-1, 21 if cov is None else 36)
+    if len(s) != n:
+        raise FgoError("plane_check_vro_batch: info / cov needs one entry per record")
+    mi = max(int(ip[-1]), 0)
+    match = np.zeros(mi, np.int64); d2 = np.zeros(mi); raw = np.zeros(mi); sdj = np.zeros(mi)
+    pred = np.zeros((mi, 4)); pcov = np.zeros((mi, 3, 3))
+    res = (PlaneCheckResult * max(n, 1))()
+    rc = lib.fgo_plane_check_vro_batch(device, n, _dp(ps), _dp(s) if cov is None else None, None if cov is None else _dp(s),
+                                       _i64p(ip), _dp(planes[0]), _dp(planes[1]), _i64p(jp), _dp(planes[2]), _dp(planes[3]),
+                                       None if params is None else C.byref(params), res, _i64p(match), _dp(d2), _dp(raw), _dp(pred),
+                                       _dp(pcov), _dp(sdj))
+    if rc < 0:
+        raise FgoError("fgo_plane_check_vro_batch failed: %d" % rc)
+    r = np.frombuffer(res, dtype=np.dtype([("status", "i4"), ("n_matched", "i4"), ("n_bad", "i4"), ("best_i", "i4"), ("best_j", "i4"),
+                                           ("reserved", "i4"), ("err", "f8"), ("err_raw", "f8")]), count=n)
+    out = {"match": match, "d2": d2, "raw": raw, "pred_abcd": pred, "pred_cov": pcov, "sdj": sdj}
+    for k in ("status", "n_matched", "n_bad", "best_i", "best_j", "err", "err_raw"):
         out[k] = r[k].copy()
     return out
 

@@ -1,0 +1,474 @@
+// Plane check of visual-odometry records on the MI355X (gfx950, f64, wave64): what gtsam/test_plane_check_vo.cpp does for ONE record
+// (computePlaneNodeDis :328-379, computePlaneDis :383-445) -- the planes seen in frame i are carried through the record's relative
+// pose Tij into frame j, paired with the planes seen there, every pair gets a Mahalanobis distance that accounts for the
+// uncertainty of the pose (Sij = information^-1, :167) and of both plane fits, and the record keeps the largest distance;
+// gtsam/test/delete_vo_by_plane_check.cpp then drops the records whose distance is too large.  The records are independent, so
+// fgo_plane_check_vro_batch runs ONE WAVE PER RECORD and all records in one launch.
+//
+//   plane i      PE = Pi.transform(Tij): n' = R^T n, d' = n.t + d, with D_pose (3x6, tangent [omega; v]) and D_plane (3x3) as
+//                dev::plane_factor<true> forms them;  S_Pi = diag(B(n)^T S_n B(n), S_d);
+//                S_PE = D_pose Sij D_pose^T + D_plane S_Pi D_plane^T;   sdj = S_d + n^T S_t n + g^T S_n g, g = (I - n n^T) t
+//                (CGraphGT::computeSdj, gtsam/gtsam_graph.cpp:725-748)
+//   matching     plane i takes the first j, in order, with |n'.n_j| >= cos_min and |d' - d_j| <= d_max (:338-362)
+//   pair         e = PE.errorVector(Pj) = [B(n')^T n_j; d' - d_j], raw = e.e, S_e = H1 S_PE H1^T + H2 S_Pj H2^T, d2 = e^T S_e^-1 e
+//                (3x3 Cholesky); H2 = diag(B(n')^T B(n_j), -1), H1 = diag(Hp, 1) with Hp the derivative of B(n')^T n_j along
+//                n' -> retract(n', v), taken through the basis rule with its axis held fixed (GTSAM 4.0's Unit3::errorVector)
+//   record       err = the largest d2 over the matched planes i (strict >, in order of i), err_raw = that pair's raw
+//
+// Schedule of a wave: every lane inverts the record's information redundantly (6x6 Cholesky in registers), so Sij and the
+// record's status are wave-uniform without a broadcast.  The planes i are then taken 64 at a time: lane l transforms plane l of the
+// block and stages n', d', S_PE in LDS; the block's candidate pairs (i, j), i-major, are owned by lanes in chunks of 64; the first
+// matching j of an i is the lowest set bit of the chunk's ballot among that i's lanes, and whether the i that straddles a chunk
+// boundary has matched already is carried (wave-uniform) into the next chunk; only the selected pairs do the Jacobian and Cholesky
+// work, and leave d2 / raw / j in the LDS slot of their i; lane l folds plane l into its running maximum.  One ordered butterfly
+// at the end gives the record's maximum (ties to the smaller i).  LDS holds one block of 64 planes, so the number of planes per
+// frame is not capped.  Every small loop is unrolled with compile-time indices, no atomics, every sum in a fixed order that
+// depends on nothing but the record: results are bit-identical from call to call and do not depend on what else is in the batch.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <climits>
+#include <cmath>
+#include "../../include/fgo.h"
+#include "device_plan.hpp"
+#include "factors_device.hpp"
+
+namespace fgo {
+using namespace dev;
+
+namespace {
+
+// LDS rows of 64 doubles, one column per plane i of the block
+constexpr int PC_N = 0, PC_D = 3, PC_S = 4, PC_D2 = 10, PC_RAW = 11, PC_ROWS = 12;
+
+struct PcArgs {
+  int64_t n;
+  const double *pose, *info, *cov;
+  const int64_t *pi_ptr, *pj_ptr;
+  const double *pi_abcd, *pi_cov, *pj_abcd, *pj_cov;
+  double cos_min, d_max, failed00;
+  fgo_plane_check_result *res;
+  int64_t *match;                                  // the per-plane outputs may be NULL
+  double *d2, *raw, *pred, *pred_cov, *sdj;
+};
+
+__device__ __forceinline__ constexpr int lt(int r, int c) { return r * (r + 1) / 2 + c; }           // lower triangle packed by rows
+__device__ __forceinline__ constexpr int ut(int r, int c) { return r * 6 - r * (r - 1) / 2 + c - r; }   // upper triangle of a 6x6, by rows
+
+// lower Cholesky factor (l00 l10 l11 l20 l21 l22) of the symmetric 3x3 matrix a00 a10 a11 a20 a21 a22; false if a pivot is not
+// positive (NaN included): the factor then carries a unit pivot there and nothing downstream divides by zero
+__device__ __forceinline__ bool chol3(double a00, double a10, double a11, double a20, double a21, double a22, double l[6]) {
+  const bool ok0 = a00 > 0;
+  l[0] = sqrt(ok0 ? a00 : 1.0);
+  l[1] = a10 / l[0];
+  l[3] = a20 / l[0];
+  const double s1 = a11 - l[1] * l[1];
+  const bool ok1 = s1 > 0;
+  l[2] = sqrt(ok1 ? s1 : 1.0);
+  l[4] = (a21 - l[3] * l[1]) / l[2];
+  const double s2 = a22 - l[3] * l[3] - l[4] * l[4];
+  const bool ok2 = s2 > 0;
+  l[5] = sqrt(ok2 ? s2 : 1.0);
+  return ok0 && ok1 && ok2;
+}
+// y = L^-1 e, returns y^T y = e^T (L L^T)^-1 e
+__device__ __forceinline__ double solve3_sq(const double l[6], double e0, double e1, double e2) {
+  const double y0 = e0 / l[0];
+  const double y1 = (e1 - l[1] * y0) / l[2];
+  const double y2 = (e2 - l[3] * y0 - l[4] * y1) / l[5];
+  return y0 * y0 + y1 * y1 + y2 * y2;
+}
+
+// S = A^-1 (upper triangle, by rows) of the symmetric 6x6 A given by its upper triangle; false if a pivot is <= 0 or not finite
+__device__ __forceinline__ bool inv6(const double *__restrict__ a_ut, double S[21]) {
+  double a[21];
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = 0; c <= r; ++c) a[lt(r, c)] = a_ut[ut(c, r)];
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    double d = a[lt(j, j)];
+#pragma unroll
+    for (int k = 0; k < j; ++k) d -= a[lt(j, k)] * a[lt(j, k)];
+    const bool okj = d > 0 && d < __builtin_huge_val();
+    ok = ok && okj;
+    const double l = sqrt(okj ? d : 1.0);
+    a[lt(j, j)] = l;
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      double s = a[lt(i, j)];
+#pragma unroll
+      for (int k = 0; k < j; ++k) s -= a[lt(i, k)] * a[lt(j, k)];
+      a[lt(i, j)] = s / l;
+    }
+  }
+  double Mi[21];                                   // L^-1, lower, packed by rows
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    Mi[lt(c, c)] = 1.0 / a[lt(c, c)];
+#pragma unroll
+    for (int r = c + 1; r < 6; ++r) {
+      double s = 0;
+#pragma unroll
+      for (int k = c; k < r; ++k) s += a[lt(r, k)] * Mi[lt(k, c)];
+      Mi[lt(r, c)] = -s / a[lt(r, r)];
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = r; c < 6; ++c) {                  // A^-1 = L^-T L^-1
+      double s = 0;
+#pragma unroll
+      for (int k = c; k < 6; ++k) s += Mi[lt(k, r)] * Mi[lt(k, c)];
+      S[ut(r, c)] = s;
+    }
+  return ok;
+}
+
+// the 3x3 block (r0, c0) of the symmetric 6x6 held as its upper triangle
+__device__ __forceinline__ M3 block3(const double S[21], int r0, int c0) {
+  M3 B;
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      const int r = r0 + a, c = c0 + b;
+      B.m[a * 3 + b] = r <= c ? S[ut(r, c)] : S[ut(c, r)];
+    }
+  return B;
+}
+
+// (a, b, c, d) with the normal normalised, d untouched, and of CPlane::m_CP (4x4 row-major) the upper triangle of the normal block
+// and entry (3, 3)
+struct PlaneIn { V3 n; double d; M3 Sn; double Sd; };
+__device__ __forceinline__ PlaneIn load_plane(const double *__restrict__ abcd, const double *__restrict__ cov16) {
+  PlaneIn P;
+  const double nn = sqrt(abcd[0] * abcd[0] + abcd[1] * abcd[1] + abcd[2] * abcd[2]);
+  P.n = {abcd[0] / nn, abcd[1] / nn, abcd[2] / nn};
+  P.d = abcd[3];
+  P.Sn = {{cov16[0], cov16[1], cov16[2], cov16[1], cov16[5], cov16[6], cov16[2], cov16[6], cov16[10]}};
+  P.Sd = cov16[15];
+  return P;
+}
+
+// B^T S B (u00 u01 u11) of a symmetric 3x3 S
+__device__ __forceinline__ void tangent_cov(const Basis &B, const M3 &S, double u[3]) {
+  const V3 s1 = mv(S, B.b1), s2 = mv(S, B.b2);
+  u[0] = dot3(B.b1, s1); u[1] = dot3(B.b1, s2); u[2] = dot3(B.b2, s2);
+}
+
+// Q U Q^T (m00 m01 m11) of a 2x2 Q (q00 q01 q10 q11) and a symmetric 2x2 U (u00 u01 u11)
+__device__ __forceinline__ void congr2(const double q[4], const double u[3], double m[3]) {
+  const double a00 = q[0] * u[0] + q[1] * u[1], a01 = q[0] * u[1] + q[1] * u[2];
+  const double a10 = q[2] * u[0] + q[3] * u[1], a11 = q[2] * u[1] + q[3] * u[2];
+  m[0] = a00 * q[0] + a01 * q[1];
+  m[1] = a00 * q[2] + a01 * q[3];
+  m[2] = a10 * q[2] + a11 * q[3];
+}
+
+// Unit3::basis() with the axis it chose (the coordinate axis of the smallest |n_i|; ties: x, then y, then z) and |n x axis|
+__device__ __forceinline__ Basis unit3_basis_axis(V3 n, V3 &ax, double &nc) {
+  const double mx = fabs(n.x), my = fabs(n.y), mz = fabs(n.z);
+  ax = {0, 0, 1};
+  if (mx <= my && mx <= mz) ax = {1, 0, 0};
+  else if (my <= mx && my <= mz) ax = {0, 1, 0};
+  V3 b1 = cross(n, ax);
+  nc = sqrt(dot3(b1, b1));
+  b1 = {b1.x / nc, b1.y / nc, b1.z / nc};
+  return {b1, cross(n, b1)};
+}
+
+// The pair (PE, Pj): d2 and raw; false when S_e is not positive definite.  PE = (np, dp) with its covariance pe (upper triangle
+// p00 p01 p02 p11 p12 p22 in the tangent of PE).
+__device__ __forceinline__ bool pair_distance(V3 np, double dp, const double pe[6], const PlaneIn &Pj, double &d2, double &raw) {
+  V3 ax;
+  double nc;
+  const Basis Bp = unit3_basis_axis(np, ax, nc), Bj = unit3_basis(Pj.n);
+  const double e0 = dot3(Bp.b1, Pj.n), e1 = dot3(Bp.b2, Pj.n), e2 = dp - Pj.d;
+  raw = e0 * e0 + e1 * e1 + e2 * e2;
+  // H2 S_Pj H2^T, H2 = diag(B(n')^T B(n_j), -1)
+  const double h[4] = {dot3(Bp.b1, Bj.b1), dot3(Bp.b1, Bj.b2), dot3(Bp.b2, Bj.b1), dot3(Bp.b2, Bj.b2)};
+  double uj[3], m2[3];
+  tangent_cov(Bj, Pj.Sn, uj);
+  congr2(h, uj, m2);
+  // Hp: column k is the derivative along dn = b_k;  c = n' x axis, b1 = c / |c|, b2 = n' x b1
+  double hp[4];
+  {
+    const V3 dn[2] = {Bp.b1, Bp.b2};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const V3 dc = cross(dn[k], ax);
+      const double pr = dot3(Bp.b1, dc);
+      const V3 db1 = {(dc.x - Bp.b1.x * pr) / nc, (dc.y - Bp.b1.y * pr) / nc, (dc.z - Bp.b1.z * pr) / nc};
+      const V3 db2 = cross(dn[k], Bp.b1) + cross(np, db1);
+      hp[k] = dot3(Pj.n, db1);
+      hp[2 + k] = dot3(Pj.n, db2);
+    }
+  }
+  // H1 S_PE H1^T, H1 = diag(Hp, 1)
+  const double u1[3] = {pe[0], pe[1], pe[3]};
+  double m1[3];
+  congr2(hp, u1, m1);
+  const double w0 = hp[0] * pe[2] + hp[1] * pe[4], w1 = hp[2] * pe[2] + hp[3] * pe[4];
+  double l[6];
+  const bool pd = chol3(m1[0] + m2[0], m1[1] + m2[1], m1[2] + m2[2], w0, w1, pe[5] + Pj.Sd, l);
+  d2 = solve3_sq(l, e0, e1, e2);
+  return pd;
+}
+
+__global__ __launch_bounds__(64) void k_plane_check(PcArgs A) {
+  __shared__ double sm[PC_ROWS * 64];
+  __shared__ int sj[64], sbad[64];
+  const int64_t rec = blockIdx.x;
+  if (rec >= A.n) return;
+  const int lane = threadIdx.x;
+  const int64_t gi0 = A.pi_ptr[rec], gj0 = A.pj_ptr[rec];
+  const int ni = (int)(A.pi_ptr[rec + 1] - gi0), nj = (int)(A.pj_ptr[rec + 1] - gj0);
+
+  // Sij, in every lane
+  double S[21];
+  int status = FGO_PC_OK;
+  if (A.cov) {
+    const double *__restrict__ c = A.cov + 36 * rec;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int k = r; k < 6; ++k) S[ut(r, k)] = c[r * 6 + k];
+  } else {
+    const double *__restrict__ a = A.info + 21 * rec;
+    if (A.failed00 > 0 && a[0] == A.failed00) status = FGO_PC_SKIPPED;     // the failed-VO sentinel (:171)
+    else if (!inv6(a, S)) status = FGO_PC_NUM;
+  }
+  if (status != FGO_PC_OK) {
+    for (int i = lane; i < ni; i += 64) {
+      const int64_t g = gi0 + i;
+      if (A.match) A.match[g] = -1;
+      if (A.d2) A.d2[g] = 0;
+      if (A.raw) A.raw[g] = 0;
+      if (A.sdj) A.sdj[g] = 0;
+      if (A.pred) for (int k = 0; k < 4; ++k) A.pred[4 * g + k] = 0;
+      if (A.pred_cov) for (int k = 0; k < 9; ++k) A.pred_cov[9 * g + k] = 0;
+    }
+    if (lane == 0) A.res[rec] = {status, 0, 0, -1, -1, 0, 0.0, 0.0};
+    return;
+  }
+
+  const double *__restrict__ ps = A.pose + 7 * rec;
+  const V3 t = {ps[0], ps[1], ps[2]};
+  const double qn = sqrt(ps[3] * ps[3] + ps[4] * ps[4] + ps[5] * ps[5] + ps[6] * ps[6]);
+  const M3 R = qmat(Q4{ps[3] / qn, ps[4] / qn, ps[5] / qn, ps[6] / qn});
+  const M3 Sww = block3(S, 0, 0), Swv = block3(S, 0, 3), Svv = block3(S, 3, 3);
+
+  double best = 0, best_raw = 0;                   // this lane's planes, in order of i
+  int best_i = -1, best_j = -1, n_matched = 0, n_bad = 0;
+
+  for (int ib = 0; ib < ni; ib += 64) {
+    const int cnt = min(64, ni - ib);
+    __syncthreads();                               // the readers of the previous block are done
+    if (lane < cnt) {
+      const int64_t g = gi0 + ib + lane;
+      const PlaneIn P = load_plane(A.pi_abcd + 4 * g, A.pi_cov + 16 * g);
+      const V3 np = mtv(R, P.n);
+      const double dp = dot3(P.n, t) + P.d;
+      const Basis Bp = unit3_basis(np), B = unit3_basis(P.n);
+      // D_pose = [[r1^T, 0], [r2^T, 0], [0, n'^T]],  r_a = b'_a x n'
+      const V3 r1 = cross(Bp.b1, np), r2 = cross(Bp.b2, np);
+      const V3 w1 = mv(Sww, r1), w2 = mv(Sww, r2), x = mv(Swv, np);
+      double pe[6] = {dot3(r1, w1), dot3(r1, w2), dot3(r1, x), dot3(r2, w2), dot3(r2, x), dot3(np, mv(Svv, np))};
+      // D_plane = [[Q, 0], [tb^T, 1]],  Q = B'^T R^T B, tb = B^T t;  S_Pi = diag(U, S_d)
+      const V3 Rb1 = mtv(R, B.b1), Rb2 = mtv(R, B.b2);
+      const double q[4] = {dot3(Bp.b1, Rb1), dot3(Bp.b1, Rb2), dot3(Bp.b2, Rb1), dot3(Bp.b2, Rb2)};
+      const double tb0 = dot3(B.b1, t), tb1 = dot3(B.b2, t);
+      double u[3], m[3];
+      tangent_cov(B, P.Sn, u);
+      congr2(q, u, m);
+      const double ut0 = u[0] * tb0 + u[1] * tb1, ut1 = u[1] * tb0 + u[2] * tb1;       // U tb
+      pe[0] += m[0]; pe[1] += m[1]; pe[3] += m[2];
+      pe[2] += q[0] * ut0 + q[1] * ut1;
+      pe[4] += q[2] * ut0 + q[3] * ut1;
+      pe[5] += tb0 * ut0 + tb1 * ut1 + P.Sd;
+      sm[(PC_N + 0) * 64 + lane] = np.x; sm[(PC_N + 1) * 64 + lane] = np.y; sm[(PC_N + 2) * 64 + lane] = np.z;
+      sm[PC_D * 64 + lane] = dp;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) sm[(PC_S + k) * 64 + lane] = pe[k];
+      sm[PC_D2 * 64 + lane] = 0; sm[PC_RAW * 64 + lane] = 0;
+      sj[lane] = -1; sbad[lane] = 0;
+      if (A.pred) { double *o = A.pred + 4 * g; o[0] = np.x; o[1] = np.y; o[2] = np.z; o[3] = dp; }
+      if (A.pred_cov) {
+        double *o = A.pred_cov + 9 * g;
+        o[0] = pe[0]; o[1] = pe[1]; o[2] = pe[2]; o[3] = pe[1]; o[4] = pe[3]; o[5] = pe[4]; o[6] = pe[2]; o[7] = pe[4]; o[8] = pe[5];
+      }
+      if (A.sdj) {
+        const double nt = dot3(P.n, t);
+        const V3 gv = {t.x - P.n.x * nt, t.y - P.n.y * nt, t.z - P.n.z * nt};
+        A.sdj[g] = P.Sd + dot3(P.n, mv(Svv, P.n)) + dot3(gv, mv(P.Sn, gv));
+      }
+    }
+    __syncthreads();
+
+    // the block's candidate pairs, i-major, 64 at a time
+    const int64_t npairs = (int64_t)cnt * nj;
+    int64_t carry_i = -1;                          // the last i of the previous chunk, and whether it has matched (wave-uniform)
+    bool carry_m = false;
+    for (int64_t base = 0; base < npairs; base += 64) {
+      const int64_t p = base + lane;
+      const bool valid = p < npairs;
+      const int64_t il = valid ? p / nj : 0;
+      const int j = (int)(p - il * nj);
+      bool cond = false;
+      V3 np = {0, 0, 0};
+      double dp = 0;
+      PlaneIn Pj;
+      if (valid) {
+        np = {sm[(PC_N + 0) * 64 + il], sm[(PC_N + 1) * 64 + il], sm[(PC_N + 2) * 64 + il]};
+        dp = sm[PC_D * 64 + il];
+        Pj = load_plane(A.pj_abcd + 4 * (gj0 + j), A.pj_cov + 16 * (gj0 + j));
+        cond = fabs(dot3(np, Pj.n)) >= A.cos_min && fabs(dp - Pj.d) <= A.d_max;
+      }
+      const unsigned long long mask = __ballot(cond);
+      const int64_t s = il * nj - base;            // the chunk's lanes of this i begin at lo
+      const int lo = s > 0 ? (int)s : 0;
+      const unsigned long long mine = mask & ((1ull << lane) - 1) & ~((1ull << lo) - 1);
+      const bool sel = cond && mine == 0 && !(il == carry_i && carry_m);
+      const int64_t last_p = (base + 63 < npairs ? base + 63 : npairs - 1), last_i = last_p / nj, sl = last_i * nj - base;
+      const bool any_last = (mask >> (sl > 0 ? (int)sl : 0)) != 0;
+      carry_m = (last_i == carry_i && carry_m) || any_last;
+      carry_i = last_i;
+      if (sel) {
+        double pe[6], d2, raw;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) pe[k] = sm[(PC_S + k) * 64 + il];
+        const bool pd = pair_distance(np, dp, pe, Pj, d2, raw);
+        sm[PC_D2 * 64 + il] = pd ? d2 : __builtin_huge_val();
+        sm[PC_RAW * 64 + il] = pd ? raw : __builtin_huge_val();
+        sj[il] = j; sbad[il] = pd ? 0 : 1;
+      }
+    }
+    __syncthreads();
+    if (lane < cnt) {
+      const int64_t g = gi0 + ib + lane;
+      const int mj = sj[lane];
+      const double d2 = sm[PC_D2 * 64 + lane], raw = sm[PC_RAW * 64 + lane];
+      if (A.match) A.match[g] = mj;
+      if (A.d2) A.d2[g] = d2;
+      if (A.raw) A.raw[g] = raw;
+      if (mj >= 0) {
+        ++n_matched;
+        if (sbad[lane]) ++n_bad;
+        else if (d2 > best) { best = d2; best_raw = raw; best_i = ib + lane; best_j = mj; }
+      }
+    }
+  }
+
+  // the record's maximum: the larger d2, a tie to the smaller i -- what strict > in order of i keeps.  Both sides of a step
+  // compare the same two candidates, so every lane ends with the same record.
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ob = __shfl_xor(best, o, 64), oraw = __shfl_xor(best_raw, o, 64);
+    const int oi = __shfl_xor(best_i, o, 64), oj = __shfl_xor(best_j, o, 64);
+    n_matched += __shfl_xor(n_matched, o, 64);
+    n_bad += __shfl_xor(n_bad, o, 64);
+    if (ob > best || (ob == best && oi >= 0 && oi < best_i)) { best = ob; best_raw = oraw; best_i = oi; best_j = oj; }
+  }
+  if (lane == 0) A.res[rec] = {FGO_PC_OK, n_matched, n_bad, best_i, best_j, 0, best, best_raw};
+}
+
+// Every device array of a call lives in ONE allocation: a call costs one hipMalloc / hipFree whatever it asks for.  reserve() hands
+// out offsets (256-byte aligned) before the allocation is made, at() turns them into pointers afterwards.
+struct Arena {
+  char *base = nullptr;
+  size_t total = 0;
+  ~Arena() { if (base) (void)hipFree(base); }
+  size_t reserve(size_t bytes) { const size_t o = total; total += (bytes + 255) & ~(size_t)255; return o; }
+  hipError_t alloc() { return hipMalloc((void **)&base, total ? total : 1); }
+  template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(base + off); }
+};
+// a ptr array is non-negative and non-decreasing, and no record holds more planes than an int counts
+bool ptr_ok(const int64_t *ptr, int64_t n) {
+  if (ptr[0] < 0) return false;
+  for (int64_t r = 0; r < n; ++r)
+    if (ptr[r + 1] < ptr[r] || ptr[r + 1] - ptr[r] > INT_MAX) return false;
+  return true;
+}
+bool normals_ok(const double *abcd, int64_t first, int64_t last) {
+  for (int64_t k = first; k < last; ++k) {
+    const double *a = abcd + 4 * k, nn = a[0] * a[0] + a[1] * a[1] + a[2] * a[2];
+    if (!(nn > 0) || !std::isfinite(nn)) return false;
+  }
+  return true;
+}
+
+}  // namespace
+}  // namespace fgo
+
+extern "C" void fgo_plane_check_params_default(fgo_plane_check_params *p) {
+  if (!p) return;
+  p->cos_min = cos(10. * M_PI / 180.);
+  p->d_max = 0.2;
+  p->failed_info00 = 10000.0;
+}
+
+extern "C" int fgo_plane_check_vro_batch(int device, int64_t n_records, const double *pose_ij7, const double *info_ut21, const double *cov36,
+                                         const int64_t *pi_ptr, const double *pi_abcd, const double *pi_cov16, const int64_t *pj_ptr,
+                                         const double *pj_abcd, const double *pj_cov16, const fgo_plane_check_params *params,
+                                         fgo_plane_check_result *result, int64_t *match_out, double *d2_out, double *raw_out,
+                                         double *pred_abcd_out, double *pred_cov9_out, double *sdj_out) {
+  using namespace fgo;
+  fgo_plane_check_params P;
+  fgo_plane_check_params_default(&P);
+  if (params) P = *params;
+  if (n_records < 0 || n_records > INT_MAX || !(P.cos_min >= -1 && P.cos_min <= 1) || !(P.d_max >= 0)) return FGO_EINVAL;
+  if (n_records == 0) return FGO_OK;
+  if (!pose_ij7 || !pi_ptr || !pj_ptr || !result || (info_ut21 != nullptr) == (cov36 != nullptr)) return FGO_EINVAL;
+  if (!ptr_ok(pi_ptr, n_records) || !ptr_ok(pj_ptr, n_records)) return FGO_EINVAL;
+  const int64_t Mi = pi_ptr[n_records], Mj = pj_ptr[n_records];
+  if ((Mi > 0 && (!pi_abcd || !pi_cov16)) || (Mj > 0 && (!pj_abcd || !pj_cov16))) return FGO_EINVAL;
+  for (int64_t r = 0; r < n_records; ++r) {
+    const double *q = pose_ij7 + 7 * r + 3, qq = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+    if (!(qq > 0) || !std::isfinite(qq)) return FGO_EINVAL;
+  }
+  if (!normals_ok(pi_abcd, pi_ptr[0], Mi) || !normals_ok(pj_abcd, pj_ptr[0], Mj)) return FGO_EINVAL;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FGO_ENODEV;   // no CPU fallback
+  if (hipSetDevice(device) != hipSuccess) return FGO_ENODEV;
+  const size_t n = (size_t)n_records, mi = (size_t)Mi, mj = (size_t)Mj, D = sizeof(double);
+  Arena M;
+  // inputs (host pointer, bytes), then the result records, then the per-plane outputs that were asked for
+  const void *in_host[8] = {pose_ij7, info_ut21 ? info_ut21 : cov36, pi_ptr, pj_ptr, pi_abcd, pi_cov16, pj_abcd, pj_cov16};
+  const size_t in_bytes[8] = {7 * n * D, (info_ut21 ? 21 : 36) * n * D, (n + 1) * sizeof(int64_t), (n + 1) * sizeof(int64_t),
+                              4 * mi * D, 16 * mi * D, 4 * mj * D, 16 * mj * D};
+  size_t in_off[8];
+  for (int k = 0; k < 8; ++k) in_off[k] = M.reserve(in_bytes[k]);
+  const size_t res_off = M.reserve(n * sizeof(fgo_plane_check_result));
+  void *out_host[6] = {match_out, d2_out, raw_out, pred_abcd_out, pred_cov9_out, sdj_out};
+  const size_t out_bytes[6] = {mi * sizeof(int64_t), mi * D, mi * D, 4 * mi * D, 9 * mi * D, mi * D};
+  size_t out_off[6];
+  for (int k = 0; k < 6; ++k) out_off[k] = out_host[k] ? M.reserve(out_bytes[k]) : 0;
+  if (M.alloc() != hipSuccess) return FGO_ENOMEM;
+  for (int k = 0; k < 8; ++k)
+    if (in_bytes[k] && hipMemcpy(M.at<char>(in_off[k]), in_host[k], in_bytes[k], hipMemcpyHostToDevice) != hipSuccess) return FGO_ENUM;
+  PcArgs A;
+  A.n = n_records;
+  A.pose = M.at<double>(in_off[0]);
+  A.info = info_ut21 ? M.at<double>(in_off[1]) : nullptr;
+  A.cov = cov36 ? M.at<double>(in_off[1]) : nullptr;
+  A.pi_ptr = M.at<int64_t>(in_off[2]); A.pj_ptr = M.at<int64_t>(in_off[3]);
+  A.pi_abcd = M.at<double>(in_off[4]); A.pi_cov = M.at<double>(in_off[5]);
+  A.pj_abcd = M.at<double>(in_off[6]); A.pj_cov = M.at<double>(in_off[7]);
+  A.cos_min = P.cos_min; A.d_max = P.d_max; A.failed00 = P.failed_info00;
+  A.res = M.at<fgo_plane_check_result>(res_off);
+  A.match = match_out ? M.at<int64_t>(out_off[0]) : nullptr;
+  A.d2 = d2_out ? M.at<double>(out_off[1]) : nullptr;
+  A.raw = raw_out ? M.at<double>(out_off[2]) : nullptr;
+  A.pred = pred_abcd_out ? M.at<double>(out_off[3]) : nullptr;
+  A.pred_cov = pred_cov9_out ? M.at<double>(out_off[4]) : nullptr;
+  A.sdj = sdj_out ? M.at<double>(out_off[5]) : nullptr;
+  hipLaunchKernelGGL(k_plane_check, dim3((unsigned)n_records), dim3(64), 0, 0, A);
+  if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return FGO_ENUM;
+  if (hipMemcpy(result, A.res, n * sizeof(fgo_plane_check_result), hipMemcpyDeviceToHost) != hipSuccess) return FGO_ENUM;
+  for (int k = 0; k < 6; ++k)
+    if (out_host[k] && out_bytes[k] && hipMemcpy(out_host[k], M.at<char>(out_off[k]), out_bytes[k], hipMemcpyDeviceToHost) != hipSuccess) return FGO_ENUM;
+  return FGO_OK;
+}

@@ -162,6 +162,59 @@ int fgo_two_view_ba_batch(int device, int64_t n_pairs, const int64_t *match_ptr 
                           double *pose_j_out /* n x 7 */, double *pose_i_out /* n x 7, may be NULL */,
                           double *cov36_out /* n x 36, may be NULL */, double *info_ut21_out /* n x 21, may be NULL */,
                           fgo_two_view_result *result /* n */);
+/* Plane check of visual-odometry records, batched: what gtsam/test_plane_check_vo.cpp does record after record
+ * (computePlaneNodeDis :328-379, computePlaneDis :383-445; gtsam/test/delete_vo_by_plane_check.cpp consumes its log and sets the
+ * information of the rejected records to the 10000 sentinel, :189), for n_records independent records in ONE launch, one wave
+ * per record.  Record r has the relative pose Tij = pose_ij7[r] (t(3) q_xyzw(4), the pose of frame j in frame i: Pose3(final_trafo),
+ * :165-166; the quaternion is normalised on entry) and the covariance Sij: either info_ut21[r]^-1 (:167; the 21 upper-triangular
+ * entries in tangent [omega; v] that fgo_two_view_ba_batch writes, inverted on the device by a 6x6 Cholesky factorisation) or
+ * cov36[r] as given (6x6 row-major, only its upper triangle is read; it has to be positive semi-definite, which is not tested,
+ * and the sentinel does not apply).  Exactly one of the two is passed, the other is NULL.  The record owns the planes
+ * [pi_ptr[r], pi_ptr[r+1]) seen in frame i and [pj_ptr[r], pj_ptr[r+1]) seen in frame j.  A plane is (a, b, c, d): the normal is
+ * normalised on entry and d left untouched, as fgo_add_plane_factor does; cov16 is CPlane::m_CP (4x4 row-major), of which the
+ * upper triangle of the 3x3 normal block S_n and entry (3, 3) S_d are read.  The tangent covariance of a plane is
+ * S_P = diag(B^T S_n B, S_d), B = Unit3::basis(n) (:395-406).
+ *   plane i     PE = Pi.transform(Tij): n' = R^T n, d' = n.t + d, with the Jacobians D_pose (3x6) and D_plane (3x3) of
+ *               OrientedPlane3::transform;  S_PE = D_pose Sij D_pose^T + D_plane S_Pi D_plane^T (:409).
+ *               pred_abcd_out = PE, pred_cov9_out = S_PE (row-major, in the tangent of PE),
+ *               sdj_out = S_di + n^T S_t n + g^T S_ni g, g = (I - n n^T) t, S_t = Sij[3:6, 3:6]  (CGraphGT::computeSdj,
+ *               gtsam/gtsam_graph.cpp:725-748, with CP(3, 3) standing in for m_E_Sdi)
+ *   matching    planes i are taken in order; plane i takes the FIRST j, in order, with |n'.n_j| >= cos_min and
+ *               |d' - d_j| <= d_max (:338-362); several i may take the same j.  match_out[i] = the index of that j within the
+ *               record's own j-list, or -1
+ *   pair        e = PE.errorVector(Pj) = [B(n')^T n_j; d' - d_j], raw = e.e, S_e = H1 S_PE H1^T + H2 S_Pj H2^T,
+ *               d2 = e^T S_e^-1 e by a 3x3 Cholesky factorisation;  H2 = diag(B(n')^T B(n_j), -1), H1 = diag(Hp, 1) with Hp the
+ *               derivative of B(n')^T n_j along n' -> retract(n', v), taken through the basis rule with the axis choice held
+ *               fixed (GTSAM 4.0's Unit3::errorVector).  A pair whose S_e is not positive definite is counted in n_bad, gets
+ *               d2_out = raw_out = +inf and takes no part in the maximum.  Unmatched planes: d2_out = raw_out = 0
+ *   record      err = the largest d2 over the matched planes i, by strict > in order of i from 0 (a tie stays with the earlier
+ *               i), err_raw = that pair's raw, best_i / best_j = that pair (indices within the record's lists), -1 when
+ *               no pair raised err above 0;  n_matched = planes i that took a j (the bad ones included)
+ * A record whose status is not FGO_PC_OK has err = err_raw = 0, nothing matched (match_out = -1) and every other per-plane
+ * output zero.  Stateless, host arrays in and out, like fgo_two_view_ba_batch.  FGO_EINVAL (before any HIP call): a NULL
+ * required pointer, both or neither of info_ut21 / cov36, a negative or decreasing ptr array (or more than INT_MAX planes in one
+ * list), a zero quaternion or a zero normal, cos_min outside [-1, 1], d_max < 0; FGO_ENODEV without a HIP device (no CPU
+ * fallback).  n_records == 0: FGO_OK.  A record's result never depends on what else is in the batch. */
+typedef struct {
+  double cos_min;        /* cos(10 deg)   test_plane_check_vo.cpp:330,355 */
+  double d_max;          /* 0.2           :355 */
+  double failed_info00;  /* 10000: information (0,0) == this marks a failed VO record (:171); <= 0 disables the test */
+} fgo_plane_check_params;
+void fgo_plane_check_params_default(fgo_plane_check_params *p);      /* NULL tolerated */
+#define FGO_PC_OK 0
+#define FGO_PC_SKIPPED 1   /* failed-VO sentinel: err = err_raw = 0, nothing matched (:171-176) */
+#define FGO_PC_NUM 2       /* the record's information is not positive definite (a pivot <= 0 or non-finite): err = err_raw = 0 */
+typedef struct { int status, n_matched, n_bad, best_i, best_j, reserved; double err, err_raw; } fgo_plane_check_result;
+int fgo_plane_check_vro_batch(int device, int64_t n_records,
+                              const double *pose_ij7 /* n x 7 */,
+                              const double *info_ut21 /* n x 21, or NULL */, const double *cov36 /* n x 36, or NULL */,
+                              const int64_t *pi_ptr /* n + 1 */, const double *pi_abcd /* Mi x 4 */, const double *pi_cov16 /* Mi x 16 */,
+                              const int64_t *pj_ptr /* n + 1 */, const double *pj_abcd /* Mj x 4 */, const double *pj_cov16 /* Mj x 16 */,
+                              const fgo_plane_check_params *params /* NULL = defaults */,
+                              fgo_plane_check_result *result /* n */,
+                              int64_t *match_out /* Mi */, double *d2_out /* Mi */, double *raw_out /* Mi */,
+                              double *pred_abcd_out /* Mi x 4 */, double *pred_cov9_out /* Mi x 9 */,
+                              double *sdj_out /* Mi */);   /* each of the six may be NULL */
 /* ---- IMU: velocity / bias variables, their priors, preintegration and the CombinedImuFactor.
  *      Values::insert(V(id), Vector3) / insert(B(id), imuBias::ConstantBias) + PriorFactor<Vector3>(Isotropic::Sigma(3,
  *      1e-3)) / PriorFactor<ConstantBias>(Isotropic::Sigma(6, 1e-3)) — gtsam/gtsam_graph.cpp:346-367.
