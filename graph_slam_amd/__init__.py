@@ -68,6 +68,19 @@ class PlaneCheckResult(C.Structure):
 
 FGO_PC_OK, FGO_PC_SKIPPED, FGO_PC_NUM = 0, 1, 2
 
+
+class ImuCheckParams(C.Structure):
+    """fgo_imu_check_params"""
+    _fields_ = [("d2_gate", C.c_double), ("d2_ref_gate", C.c_double), ("failed_info00", C.c_double)]
+
+
+class ImuCheckResult(C.Structure):
+    """fgo_imu_check_result"""
+    _fields_ = [("status", C.c_int), ("reject", C.c_int), ("d2", C.c_double), ("d2_ref", C.c_double), ("angle", C.c_double)]
+
+
+FGO_IC_OK, FGO_IC_SKIPPED, FGO_IC_NUM = 0, 1, 2
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)     # fgo_allreduce_fn
 
 
@@ -153,6 +166,12 @@ def _load():
     lib.fgo_plane_check_params_default.argtypes = [C.POINTER(PlaneCheckParams)]
     lib.fgo_plane_check_vro_batch.argtypes = [C.c_int, C.c_int64, dp, dp, dp, i64p, dp, dp, i64p, dp, dp, C.POINTER(PlaneCheckParams),
                                               C.POINTER(PlaneCheckResult), i64p, dp, dp, dp, dp, dp]
+    lib.fgo_chi2_quantile.restype = C.c_double
+    lib.fgo_chi2_quantile.argtypes = [C.c_int, C.c_double]
+    lib.fgo_imu_check_params_default.restype = None
+    lib.fgo_imu_check_params_default.argtypes = [C.POINTER(ImuCheckParams)]
+    lib.fgo_imu_check_vro_batch.argtypes = [C.c_int, C.c_int64, dp, dp, dp, C.c_int64, dp, i64p, dp, dp, C.POINTER(ImuCheckParams),
+                                            C.POINTER(ImuCheckResult), dp, dp]
     lib.fgo_add_vec3.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_bias.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_prior_vec3.argtypes = [C.c_void_p, C.c_int64, dp, C.c_double]
@@ -309,6 +328,66 @@ def plane_check_vro_batch(pose_ij, pi_ptr, pi_abcd, pi_cov, pj_ptr, pj_abcd, pj_
     out = {"match": match, "d2": d2, "raw": raw, "pred_abcd": pred, "pred_cov": pcov, "sdj": sdj}
     for k in ("status", "n_matched", "n_bad", "best_i", "best_j", "err", "err_raw"):
         out[k] = r[k].copy()
+    return out
+
+
+def chi2_quantile(dof, p):
+    """fgo_chi2_quantile: the reference's utils::chi2(dof, alpha), the quantile of chi-square(dof) at probability p"""
+    return float(lib.fgo_chi2_quantile(int(dof), float(p)))
+
+
+def imu_check_params(**kw):
+    """fgo_imu_check_params_default, with the given fields replaced"""
+    p = ImuCheckParams()
+    lib.fgo_imu_check_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(ImuCheckParams._fields_):
+            raise TypeError("fgo_imu_check_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def imu_check_vro_batch(pose_ij, preint, preint_index, info=None, cov=None, bias_i=None, imu_q_cam=None, params=None, device=0,
+                        want_dw=False, want_cov=False):
+    """fgo_imu_check_vro_batch: the chi-square test of gtsam/test_vro_imu_graph.cpp:679-778 for every record in one launch, one wave
+    per record.  Record r has the pose pose_ij[r] (n x 7, camera frame) with either info[r] (n x 21, what two_view_ba_batch returns)
+    or cov[r] (n x 6 x 6) and is tested against the preintegration preint[preint_index[r]]; preint is the [n_preint, PREINT_DOUBLES]
+    array preint_batch returns (or rows of Preintegrator.buf), bias_i (n x 6: acc, gyro) the bias at frame i (None = each
+    preintegration's own), imu_q_cam the rotation of the camera in the IMU frame (x y z w, None = identity).  Returns a dict of
+    arrays over the records: status (FGO_IC_*), reject (bit 0: d2 > d2_gate, bit 1: d2_ref > d2_ref_gate), d2, d2_ref, angle, and
+    dw (n x 3) / cov_dw (n x 3 x 3) when asked for."""
+    ps = np.ascontiguousarray(pose_ij, np.float64).reshape(-1, 7)
+    n = len(ps)
+    pm = np.ascontiguousarray(preint, np.float64).reshape(-1, PREINT_DOUBLES)
+    ix = np.ascontiguousarray(preint_index, np.int64).reshape(-1)
+    if len(ix) != n:
+        raise FgoError("imu_check_vro_batch: preint_index needs one entry per record")
+    if (info is None) == (cov is None):
+        raise FgoError("imu_check_vro_batch: exactly one of info (n x 21) and cov (n x 6 x 6)")
+    s = np.ascontiguousarray(info if cov is None else cov, np.float64).reshape(-1, 21 if cov is None else 36)
+    if len(s) != n:
+        raise FgoError("imu_check_vro_batch: info / cov needs one entry per record")
+    b = None if bias_i is None else np.ascontiguousarray(bias_i, np.float64).reshape(-1, 6)
+    if b is not None and len(b) != n:
+        raise FgoError("imu_check_vro_batch: bias_i needs one entry per record")
+    q = None if imu_q_cam is None else np.ascontiguousarray(imu_q_cam, np.float64)
+    if q is not None and q.shape != (4,):
+        raise FgoError("imu_check_vro_batch: imu_q_cam = x y z w")
+    dw = np.zeros((n, 3)) if want_dw else None
+    cdw = np.zeros((n, 3, 3)) if want_cov else None
+    res = (ImuCheckResult * max(n, 1))()
+    opt = lambda a: None if a is None else _dp(a)
+    rc = lib.fgo_imu_check_vro_batch(device, n, _dp(ps), _dp(s) if cov is None else None, None if cov is None else _dp(s), len(pm),
+                                     _dp(pm), _i64p(ix), opt(b), opt(q), None if params is None else C.byref(params), res, opt(dw),
+                                     opt(cdw))
+    if rc < 0:
+        raise FgoError("fgo_imu_check_vro_batch failed: %d" % rc)
+    r = np.frombuffer(res, dtype=np.dtype([("status", "i4"), ("reject", "i4"), ("d2", "f8"), ("d2_ref", "f8"), ("angle", "f8")]), count=n)
+    out = {k: r[k].copy() for k in ("status", "reject", "d2", "d2_ref", "angle")}
+    if want_dw:
+        out["dw"] = dw
+    if want_cov:
+        out["cov_dw"] = cdw
     return out
 
 

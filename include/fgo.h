@@ -215,6 +215,10 @@ int fgo_plane_check_vro_batch(int device, int64_t n_records,
                               int64_t *match_out /* Mi */, double *d2_out /* Mi */, double *raw_out /* Mi */,
                               double *pred_abcd_out /* Mi x 4 */, double *pred_cov9_out /* Mi x 9 */,
                               double *sdj_out /* Mi */);   /* each of the six may be NULL */
+/* utils::chi2(dof, alpha) = boost::math::quantile(chi_squared(dof), alpha) (gtsam/chi2.h:17-26): the x with P(dof / 2, x / 2) = p, P the
+ * regularised lower incomplete gamma function (series below x = a + 1, continued fraction above), inverted by a safeguarded Newton
+ * iteration from the Wilson-Hilferty start.  Host only.  dof < 1: 0 (as the reference returns); p <= 0: 0; p >= 1: +inf; p NaN: NaN. */
+double fgo_chi2_quantile(int dof, double p);
 /* ---- IMU: velocity / bias variables, their priors, preintegration and the CombinedImuFactor.
  *      Values::insert(V(id), Vector3) / insert(B(id), imuBias::ConstantBias) + PriorFactor<Vector3>(Isotropic::Sigma(3,
  *      1e-3)) / PriorFactor<ConstantBias>(Isotropic::Sigma(6, 1e-3)) — gtsam/gtsam_graph.cpp:346-367.
@@ -260,6 +264,53 @@ int fgo_add_imu_combined(fgo_ctx *ctx, const int64_t ids6[6] /* Xi Vi Xj Vj Bi B
  * preintMeasCov^-1 by Cholesky, symmetrised -- noiseModel::Gaussian::Covariance(pim.preintMeasCov()) in GTSAM terms.
  * Host-only; FGO_ENUM if the covariance is not positive definite. */
 int fgo_preint_information(const fgo_preint *preint, double info225[225]);
+/* IMU check of visual-odometry records, batched: the chi-square test the chi2_for_vro switch turns on in the reference's drivers
+ * (gtsam/test_vro_imu_graph.cpp:679-778; g_chi2_test :52, :496; the switch is read in test_ba_imu_graph.cpp:575 and
+ * test_plane_check_vo.cpp:467 as well) -- the rotation of a record against the rotation the IMU preintegrated between the same
+ * two key frames -- for n_records independent records in ONE launch, one wave per record.  Record r has the relative pose
+ * pose_ij7[r] (t(3) q_xyzw(4) in the camera frame, as fgo_plane_check_vro_batch takes it; only the quaternion is read, and it is
+ * normalised on entry) with the covariance Sij: info_ut21[r]^-1 (6x6 Cholesky on the device, tangent [omega; v]) or cov36[r] (6x6
+ * row-major, only the upper triangle of its leading 3x3 block is read); exactly one of the two is passed.  It is tested against
+ * preint[preint_index[r]] (what fgo_preint_batch / fgo_preint_integrate produce; several records may name the same one) at the
+ * bias bias_i6[r] (acc(3), gyro(3); NULL = every preintegration's own bhat).  imu_q_cam4 is the rotation R_uc of *mp_u2c (x y z w,
+ * normalised on entry, NULL = identity): the omega rows of the adjoint hold nothing but R, so its translation does not enter.
+ *   dR_imu = dR Exp(J_R_bg (bg_i - bhat_g))   the rotation of pre_p.transform_pose_to(cur_state.pose()) (:708-710), corrected as
+ *                                             fgo_preint_predict corrects it
+ *   dR_vro = R_uc R(q_ij) R_uc^T              (:692-698)
+ *   dRw = dR_imu^T dR_vro, dw = Logmap(dRw), angle = |dw|, D = the inverse right Jacobian at dw;
+ *   J_imu = -D dRw^T (Rot3::between's H1 through Logmap's Jacobian, :714-717), J_vro = D (the term the reference has commented out)
+ *   calibrated   S = J_imu Sth J_imu^T + J_vro (R_uc Sij[0:3, 0:3] R_uc^T) J_vro^T with Sth = preintMeasCov[0:3, 0:3];
+ *                d2 = dw^T S^-1 dw by a 3x3 Cholesky: chi-square with 3 degrees of freedom for a consistent record.
+ *                cov_dw9_out = S (row-major, exactly symmetric), dw_out = dw
+ *   reference    Lth = (preintMeasCov^-1)[0:3, 0:3], d2_ref = dw^T (J_imu Lth J_imu^T) dw (:724-743): an information-weighted norm
+ *                that leaves the record's own uncertainty out and is not chi-square distributed; the 15x15 inverse is
+ *                not formed: the covariance is factored with the theta block last, Lth is the inverse Gram matrix of the factor's
+ *                trailing 3x3 triangle
+ *   reject       bit 0: d2 > d2_gate;  bit 1: d2_ref > d2_ref_gate (:753)
+ * preintMeasCov is read as (C + C^T) / 2.  A record whose status is not FGO_IC_OK has every output zero; a preintegration of no
+ * samples (covariance 0) is FGO_IC_NUM.  Stateless, host arrays in and out, like fgo_plane_check_vro_batch.  FGO_EINVAL (before any
+ * HIP call): a negative n_records, a NULL required pointer, both or neither of info_ut21 / cov36, n_preint < 1 with n_records > 0,
+ * an index outside [0, n_preint), a zero quaternion (record or extrinsic), a gate <= 0; FGO_ENODEV without a HIP device (no CPU
+ * fallback).  n_records == 0: FGO_OK.  A numerical failure of one record is that record's status; a record's result never depends
+ * on what else is in the batch, on its place in it, or on the call. */
+typedef struct {
+  double d2_gate;        /* fgo_chi2_quantile(3, 0.95) = 7.814727903251179: the CI the reference computes (:683) */
+  double d2_ref_gate;    /* 40000  (:753) */
+  double failed_info00;  /* 10000: information (0,0) == this marks a failed VO record; <= 0 disables the test */
+} fgo_imu_check_params;
+void fgo_imu_check_params_default(fgo_imu_check_params *p);          /* NULL tolerated */
+#define FGO_IC_OK 0
+#define FGO_IC_SKIPPED 1   /* failed-VO sentinel (info_ut21 mode only) */
+#define FGO_IC_NUM 2       /* the record's information, preintMeasCov or S is not positive definite (a pivot <= 0 or non-finite) */
+typedef struct { int status, reject; double d2, d2_ref, angle; } fgo_imu_check_result;
+int fgo_imu_check_vro_batch(int device, int64_t n_records,
+                            const double *pose_ij7 /* n x 7 */,
+                            const double *info_ut21 /* n x 21, or NULL */, const double *cov36 /* n x 36, or NULL */,
+                            int64_t n_preint, const fgo_preint *preint, const int64_t *preint_index /* n, each in [0, n_preint) */,
+                            const double *bias_i6 /* n x 6, or NULL */, const double imu_q_cam4[4] /* NULL = identity */,
+                            const fgo_imu_check_params *params /* NULL = defaults */,
+                            fgo_imu_check_result *result /* n */,
+                            double *dw_out /* n x 3, may be NULL */, double *cov_dw9_out /* n x 9, may be NULL */);
 
 /* LevenbergMarquardtOptimizer(graph, values).optimize() with GTSAM 4.0's default parameters —
  *      CGraphGT::optimizeGraphBatch, gtsam/gtsam_graph.cpp:1784-1788.  max_iters <= 0 selects the default 100.
