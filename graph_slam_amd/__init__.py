@@ -81,6 +81,22 @@ class ImuCheckResult(C.Structure):
 
 FGO_IC_OK, FGO_IC_SKIPPED, FGO_IC_NUM = 0, 1, 2
 
+
+class VroParams(C.Structure):
+    """fgo_vro_params"""
+    _fields_ = [("hypotheses", C.c_int), ("seed", C.c_uint64), ("max_dist", C.c_double), ("min_side", C.c_double),
+                ("rigid_tol", C.c_double), ("refine_rounds", C.c_int), ("min_inliers", C.c_int), ("fx", C.c_double), ("fy", C.c_double),
+                ("sigma_px", C.c_double), ("sigma_z", C.c_double * 3)]
+
+
+class VroResult(C.Structure):
+    """fgo_vro_result"""
+    _fields_ = [("status", C.c_int), ("n_inliers", C.c_int), ("best_hypothesis", C.c_int), ("best_count", C.c_int),
+                ("n_valid", C.c_int), ("rounds", C.c_int), ("rmse", C.c_double)]
+
+
+FGO_VRO_OK, FGO_VRO_TOO_FEW, FGO_VRO_NUM = 0, 1, 2
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)     # fgo_allreduce_fn
 
 
@@ -172,6 +188,13 @@ def _load():
     lib.fgo_imu_check_params_default.argtypes = [C.POINTER(ImuCheckParams)]
     lib.fgo_imu_check_vro_batch.argtypes = [C.c_int, C.c_int64, dp, dp, dp, C.c_int64, dp, i64p, dp, dp, C.POINTER(ImuCheckParams),
                                             C.POINTER(ImuCheckResult), dp, dp]
+    lib.fgo_vro_params_default.restype = None
+    lib.fgo_vro_params_default.argtypes = [C.POINTER(VroParams)]
+    lib.fgo_vro_ransac_batch.argtypes = [C.c_int, C.c_int64, i64p, dp, dp, C.POINTER(VroParams), dp, dp, dp, C.POINTER(C.c_ubyte),
+                                         C.POINTER(C.c_int32), C.POINTER(VroResult)]
+    lib.fgo_debug_vro_waves.argtypes = [C.c_int]
+    lib.fgo_debug_vro_kernel_ms.restype = C.c_double
+    lib.fgo_debug_vro_kernel_ms.argtypes = []
     lib.fgo_add_vec3.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_bias.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_prior_vec3.argtypes = [C.c_void_p, C.c_int64, dp, C.c_double]
@@ -388,6 +411,57 @@ def imu_check_vro_batch(pose_ij, preint, preint_index, info=None, cov=None, bias
         out["dw"] = dw
     if want_cov:
         out["cov_dw"] = cdw
+    return out
+
+
+def vro_params(**kw):
+    """fgo_vro_params_default, with the given fields replaced (sigma_z: three coefficients)"""
+    p = VroParams()
+    lib.fgo_vro_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(VroParams._fields_):
+            raise TypeError("fgo_vro_params has no field %r" % k)
+        setattr(p, k, (C.c_double * 3)(*v) if k == "sigma_z" else v)
+    return p
+
+
+def vro_ransac_batch(match_ptr, xyz_i, xyz_j, params=None, device=0, want_info=True, want_cov=True, want_inliers=True,
+                     want_hyp_counts=False):
+    """fgo_vro_ransac_batch: RANSAC registration of every pair in one launch, one workgroup per pair.  Pair p owns the matches
+    [match_ptr[p], match_ptr[p + 1]) of xyz_i / xyz_j (M x 3: the same feature in camera i / camera j).  Returns a dict of arrays
+    over the pairs: pose_ij (n x 7, p_i = R p_j + t: what two_view_ba_batch takes as pose_j0 and the two checks as pose_ij), status
+    (FGO_VRO_*), n_inliers, best_hypothesis, best_count, n_valid, rounds, rmse, and when asked for info (n x 21), cov (n x 6 x 6),
+    inliers (M, uint8), hyp_counts (n x hypotheses, int32).  A failed pair carries the void record (identity, information 10000)."""
+    mp = np.ascontiguousarray(match_ptr, np.int64)
+    n = len(mp) - 1
+    if n < 0:
+        raise FgoError("vro_ransac_batch: match_ptr needs n_pairs + 1 entries")
+    a = np.ascontiguousarray(xyz_i, np.float64).reshape(-1, 3); b = np.ascontiguousarray(xyz_j, np.float64).reshape(-1, 3)
+    m = int(mp[-1])
+    if min(len(a), len(b)) < m:
+        raise FgoError("vro_ransac_batch: match_ptr names %d matches, the arrays hold fewer" % m)
+    if params is None:
+        params = vro_params()
+    pose = np.zeros((n, 7))
+    info = np.zeros((n, 21)) if want_info else None
+    cov = np.zeros((n, 6, 6)) if want_cov else None
+    inl = np.zeros(max(m, 0), np.uint8) if want_inliers else None
+    hyp = np.zeros((n, max(params.hypotheses, 0)), np.int32) if want_hyp_counts else None
+    res = (VroResult * max(n, 1))()
+    opt = lambda x: None if x is None else _dp(x)
+    rc = lib.fgo_vro_ransac_batch(device, n, _i64p(mp), _dp(a), _dp(b), C.byref(params), _dp(pose), opt(info), opt(cov),
+                                  None if inl is None else inl.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                  None if hyp is None else hyp.ctypes.data_as(C.POINTER(C.c_int32)), res)
+    if rc < 0:
+        raise FgoError("fgo_vro_ransac_batch failed: %d" % rc)
+    fields = ("status", "n_inliers", "best_hypothesis", "best_count", "n_valid", "rounds")
+    r = np.frombuffer(res, dtype=np.dtype([(f, "i4") for f in fields] + [("rmse", "f8")]), count=n)
+    out = {"pose_ij": pose}
+    for k in fields + ("rmse",):
+        out[k] = r[k].copy()
+    for k, v in (("info", info), ("cov", cov), ("inliers", inl), ("hyp_counts", hyp)):
+        if v is not None:
+            out[k] = v
     return out
 
 

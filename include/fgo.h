@@ -311,6 +311,74 @@ int fgo_imu_check_vro_batch(int device, int64_t n_records,
                             const fgo_imu_check_params *params /* NULL = defaults */,
                             fgo_imu_check_result *result /* n */,
                             double *dw_out /* n x 3, may be NULL */, double *cov_dw9_out /* n x 9, may be NULL */);
+/* RANSAC registration of visual-odometry records, batched: the step that PRODUCES the record the three calls above consume -- a
+ * RANSAC search over matched 3-D features (m_ransac_iterations = 5000, gtsam/test/convert_vo2ba.cpp:448), a closed-form rigid fit
+ * on the inliers (getTransformFromMatches, gtsam/gtsam_graph.cpp:492), the covariance of that fit (CGraphGT::computeCovVRO,
+ * :256-277) and the void record when it fails (makeItVoid, convert_vo2ba.cpp:424-436) -- for n_pairs independent pairs in ONE
+ * launch, one workgroup per pair.  The VRO library's own arithmetic (matchNodePairVRO, getTransformFromMatches,
+ * CCameraNode::computeCov) is not part of the reference tree, so the semantics below are THIS PROJECT'S DEFINITION, pinned to the
+ * numpy restatement tests/vro_ransac_reference.py and not to the VRO library.
+ * Pair p owns the matches [match_ptr[p], match_ptr[p+1]); xyz_i[k] / xyz_j[k] are the same feature in camera i / camera j.  The
+ * result is T = (R, t) with p_i = R p_j + t, the pose of frame j in frame i (pose_j0 of fgo_two_view_ba_batch, pose_ij7 of the two
+ * checks), stored t(3) q_xyzw(4) with w >= 0.
+ *   sampling    hypothesis h draws three distinct matches a, b, c of the pair's M from counter-based integers (mod 2^64):
+ *               u_k = mix(seed + (3 h + k + 1) 0x9E3779B97F4A7C15), k = 0, 1, 2, mix the splitmix64 finaliser
+ *               (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31);
+ *               a = u0 % M;  b = u1 % (M - 1), b += (b >= a);  c = u2 % (M - 2), c += (c >= min(a, b)), c += (c >= max(a, b)).
+ *               A hypothesis depends on (seed, h, M) only.
+ *   hypothesis  in either frame the triad e1 = (p_b - p_a) / |p_b - p_a|, e3 = e1 x (p_c - p_a) normalised, e2 = e3 x e1, F = [e1 e2 e3];
+ *               R = F_i F_j^T, t = mean_i - R mean_j over the three points.  Invalid (count -1) if |p_b - p_a| < min_side or
+ *               |(p_b - p_a) x (p_c - p_a)| < min_side^2 in either frame, or a side length (ab, ac, bc) differs between the frames
+ *               by more than rigid_tol.  Otherwise count = the number of the pair's matches with |p_i - (R p_j + t)|^2 <= max_dist^2.
+ *               Winner: the largest count, ties to the lowest h.  n_valid = the number of valid hypotheses.
+ *   refinement  the set starts as the winner's inliers; refine_rounds times: least-squares fit on the set (centroids, 3x3
+ *               cross-covariance of the centred points, the rotation maximising tr(R^T C): Horn's quaternion form, the 4x4
+ *               eigenproblem by a fixed number of cyclic Jacobi sweeps), the new set = the inliers of that fit; stop early when
+ *               the set did not change.  rounds = the fits made.  Outputs: the pose of the last round (the winner's own with
+ *               refine_rounds = 0) and its inliers; rmse over them.
+ *   information Fisher information of the pose at the final fit over the final inliers, tangent [omega; v], perturbation T Exp(xi):
+ *               r_k = p_i - (R p_j + t), J_k = [-R [p_j]x, R], Sigma(p) = G diag(sigma_px^2, sigma_px^2, sigma_z(z)^2) G^T with
+ *               G = [[z / fx, 0, x / z], [0, z / fy, y / z], [0, 0, 1]], S_k = Sigma(p_i) + R Sigma(p_j) R^T,
+ *               info = sum_k J_k^T S_k^-1 J_k (a 3x3 Cholesky per match); info_ut21_out = its upper triangle as
+ *               fgo_add_edge_se3(..., FGO_TANGENT_GTSAM) and the two checks take it; cov36_out = its inverse by a 6x6 Cholesky,
+ *               exactly symmetric.
+ *   failed      any status != FGO_VRO_OK gives makeItVoid's record: pose identity, information 10000 on the diagonal, covariance
+ *               zero, inlier mask zero, n_inliers = 0, rmse = 0; best_hypothesis / best_count (-1 / -1 when no hypothesis is
+ *               valid), n_valid and rounds as found.  The two checks report such a record as skipped.
+ * Every sum over matches is a per-lane sum in match order followed by a fixed butterfly: results are bit-identical from call to call
+ * and do not depend on the rest of the batch.  Stateless, host arrays in and out, like fgo_two_view_ba_batch.  FGO_EINVAL (before
+ * any HIP call): a NULL required pointer, a negative n_pairs, a negative or decreasing match_ptr, more than INT_MAX / 3 matches in
+ * one pair, hypotheses outside [1, 2^20], max_dist / min_side / fx / fy / sigma_px <= 0, rigid_tol < 0, refine_rounds outside
+ * [0, 10], min_inliers < 3, a sigma_z coefficient < 0 or all three zero; FGO_ENODEV without a HIP device (no CPU fallback).
+ * n_pairs == 0: FGO_OK.  A numerical failure of one pair is that pair's status only. */
+typedef struct {
+  int hypotheses;        /* 5000  m_ransac_iterations (convert_vo2ba.cpp:448) */
+  uint64_t seed;         /* 0 */
+  double max_dist;       /* 0.03 m (our choice: VRO's value is not in the reference) */
+  double min_side;       /* 0.05 m */
+  double rigid_tol;      /* 0.03 m */
+  int refine_rounds;     /* 3, 0 .. 10 */
+  int min_inliers;       /* 8  (convert_vo2ba.cpp:228) */
+  double fx, fy;         /* 250.5773  (gtsam_graph.cpp:544) */
+  double sigma_px;       /* 1.0 */
+  double sigma_z[3];     /* {0.014, 0, 0}: sigma_z(z) = s0 + s1 z + s2 z^2  (0.014: gtsam_graph.cpp:379) */
+} fgo_vro_params;
+void fgo_vro_params_default(fgo_vro_params *p);            /* NULL tolerated */
+#define FGO_VRO_OK 0
+#define FGO_VRO_TOO_FEW 1   /* fewer than 3 matches, no valid hypothesis, or fewer than min_inliers inliers after any round */
+#define FGO_VRO_NUM 2       /* non-finite input reached the fit, z <= 0 on an inlier, or the information is not positive definite */
+typedef struct { int status, n_inliers, best_hypothesis, best_count, n_valid, rounds; double rmse; } fgo_vro_result;
+int fgo_vro_ransac_batch(int device, int64_t n_pairs, const int64_t *match_ptr /* n + 1 */,
+                         const double *xyz_i /* M x 3 */, const double *xyz_j /* M x 3 */,
+                         const fgo_vro_params *params /* NULL = defaults */,
+                         double *pose_ij7_out /* n x 7 */, double *info_ut21_out /* n x 21, may be NULL */,
+                         double *cov36_out /* n x 36, may be NULL */, uint8_t *inlier_out /* M, may be NULL */,
+                         int32_t *hyp_count_out /* n x hypotheses, may be NULL: for tests and diagnosis */,
+                         fgo_vro_result *result /* n */);
+/* development: waves per pair of the next fgo_vro_ransac_batch calls (1 or 4; 0 = the default), returns the value in force; and
+ * the kernel time of the last call by HIP events, ms */
+int fgo_debug_vro_waves(int waves);
+double fgo_debug_vro_kernel_ms(void);
 
 /* LevenbergMarquardtOptimizer(graph, values).optimize() with GTSAM 4.0's default parameters —
  *      CGraphGT::optimizeGraphBatch, gtsam/gtsam_graph.cpp:1784-1788.  max_iters <= 0 selects the default 100.
