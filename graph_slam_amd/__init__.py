@@ -97,6 +97,29 @@ class VroResult(C.Structure):
 
 FGO_VRO_OK, FGO_VRO_TOO_FEW, FGO_VRO_NUM = 0, 1, 2
 
+
+class PlaneExtractParams(C.Structure):
+    """fgo_plane_extract_params"""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("z_scale", C.c_double),
+                ("z_min", C.c_double), ("z_max", C.c_double), ("hypotheses", C.c_int), ("seed", C.c_uint64), ("max_dist", C.c_double),
+                ("min_area", C.c_double), ("min_pixels", C.c_int), ("max_planes", C.c_int), ("refine_rounds", C.c_int),
+                ("sigma_px", C.c_double), ("sigma_z", C.c_double * 3)]
+
+
+class PlaneExtractResult(C.Structure):
+    """fgo_plane_extract_result"""
+    _fields_ = [("status", C.c_int), ("n_planes", C.c_int), ("n_valid_pixels", C.c_int), ("rounds_run", C.c_int)]
+
+
+class PlaneExtractPlane(C.Structure):
+    """fgo_plane_extract_plane"""
+    _fields_ = [("n_pixels", C.c_int), ("best_hypothesis", C.c_int), ("best_count", C.c_int), ("n_valid_hyp", C.c_int),
+                ("fits", C.c_int), ("reserved", C.c_int), ("rmse", C.c_double), ("centroid", C.c_double * 3)]
+
+
+FGO_PX_OK, FGO_PX_NUM = 0, 2
+FGO_PX_MAX_PLANES = 8
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)     # fgo_allreduce_fn
 
 
@@ -195,6 +218,13 @@ def _load():
     lib.fgo_debug_vro_waves.argtypes = [C.c_int]
     lib.fgo_debug_vro_kernel_ms.restype = C.c_double
     lib.fgo_debug_vro_kernel_ms.argtypes = []
+    lib.fgo_plane_extract_params_default.restype = None
+    lib.fgo_plane_extract_params_default.argtypes = [C.POINTER(PlaneExtractParams)]
+    lib.fgo_plane_extract_batch.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_uint16), C.POINTER(PlaneExtractParams),
+                                            C.POINTER(PlaneExtractResult), dp, dp, dp, C.POINTER(PlaneExtractPlane),
+                                            C.POINTER(C.c_int8), C.POINTER(C.c_int32)]
+    lib.fgo_debug_plane_extract_kernel_ms.restype = C.c_double
+    lib.fgo_debug_plane_extract_kernel_ms.argtypes = []
     lib.fgo_add_vec3.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_bias.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_prior_vec3.argtypes = [C.c_void_p, C.c_int64, dp, C.c_double]
@@ -462,6 +492,64 @@ def vro_ransac_batch(match_ptr, xyz_i, xyz_j, params=None, device=0, want_info=T
     for k, v in (("info", info), ("cov", cov), ("inliers", inl), ("hyp_counts", hyp)):
         if v is not None:
             out[k] = v
+    return out
+
+
+def plane_extract_params(**kw):
+    """fgo_plane_extract_params_default, with the given fields replaced (sigma_z: three coefficients)"""
+    p = PlaneExtractParams()
+    lib.fgo_plane_extract_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(PlaneExtractParams._fields_):
+            raise TypeError("fgo_plane_extract_params has no field %r" % k)
+        setattr(p, k, (C.c_double * 3)(*v) if k == "sigma_z" else v)
+    return p
+
+
+def plane_extract_batch(depth, params=None, want_labels=False, want_hyp_counts=False, device=0):
+    """fgo_plane_extract_batch: the planes of every depth frame in one launch, one workgroup per frame.  depth is n x H x W (or
+    H x W for one frame) of uint16 depth words.  Returns a dict of arrays.  Over the frames: status (FGO_PX_*), n_planes,
+    n_valid_pixels, rounds_run; with the fixed stride max_planes per frame (the slots past n_planes are zero): abcd_all
+    (n x max_planes x 4), cov16_all (n x max_planes x 4 x 4), cov_ut6_all (n x max_planes x 6), n_pixels, best_hypothesis, best_count,
+    n_valid_hyp, fits, rmse (n x max_planes) and centroid (n x max_planes x 3); packed, as plane_check_vro_batch takes them for
+    either frame of a record: ptr (n + 1; frame f owns the planes [ptr[f], ptr[f + 1])), abcd (P x 4), cov16 (P x 16) and cov_ut6
+    (P x 6, what Graph.add_plane_factor / gate_plane_factors / associate_planes take); when asked for labels (n x H x W, int8: -2 no
+    depth, -1 no plane, k) and hyp_counts (n x max_planes x hypotheses, int32)."""
+    d = np.ascontiguousarray(depth, np.uint16)
+    if d.ndim == 2:
+        d = d[None]
+    if d.ndim != 3:
+        raise FgoError("plane_extract_batch: depth is n x H x W")
+    n, h, w = d.shape
+    if params is None:
+        params = plane_extract_params()
+    mp = min(max(params.max_planes, 1), FGO_PX_MAX_PLANES)
+    abcd = np.zeros((n, mp, 4)); cov16 = np.zeros((n, mp, 4, 4)); ut6 = np.zeros((n, mp, 6))
+    planes = (PlaneExtractPlane * max(n * mp, 1))()
+    res = (PlaneExtractResult * max(n, 1))()
+    lab = np.zeros((n, h, w), np.int8) if want_labels else None
+    hyp = np.zeros((n, mp, min(max(params.hypotheses, 0), 1 << 16)), np.int32) if want_hyp_counts else None
+    rc = lib.fgo_plane_extract_batch(device, n, w, h, d.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(params), res, _dp(abcd), _dp(cov16),
+                                     _dp(ut6), planes, None if lab is None else lab.ctypes.data_as(C.POINTER(C.c_int8)),
+                                     None if hyp is None else hyp.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc < 0:
+        raise FgoError("fgo_plane_extract_batch failed: %d" % rc)
+    fields = ("status", "n_planes", "n_valid_pixels", "rounds_run")
+    r = np.frombuffer(res, dtype=np.dtype([(f, "i4") for f in fields]), count=n)
+    out = {k: r[k].copy() for k in fields}
+    pf = ("n_pixels", "best_hypothesis", "best_count", "n_valid_hyp", "fits")
+    pl = np.frombuffer(planes, dtype=np.dtype([(f, "i4") for f in pf] + [("reserved", "i4"), ("rmse", "f8"), ("centroid", "f8", 3)]),
+                       count=n * mp).reshape(n, mp)
+    for k in pf + ("rmse", "centroid"):
+        out[k] = pl[k].copy()
+    out.update(abcd_all=abcd, cov16_all=cov16, cov_ut6_all=ut6)
+    keep = np.arange(mp)[None, :] < out["n_planes"][:, None]
+    out["ptr"] = np.concatenate([[0], np.cumsum(out["n_planes"])]).astype(np.int64)
+    out["abcd"] = abcd[keep]; out["cov16"] = cov16[keep].reshape(-1, 16); out["cov_ut6"] = ut6[keep]
+    if lab is not None:
+        out["labels"] = lab
+    if hyp is not None:
+        out["hyp_counts"] = hyp
     return out
 
 

@@ -1,0 +1,624 @@
+// Plane extraction from depth frames on the MI355X (gfx950, f64, wave64): what the reference obtains frame after frame from
+// CPlaneNode::extractPlanes(i_img, d_img, &sr4k) (gtsam/test_plane_check_vo.cpp:181,188,213; gtsam/test_ba_imu_graph.cpp:137,274,297)
+// and hands on as CPlane::m_CP -- a sequential RANSAC over the range image, a total-least-squares fit on the inliers and the
+// covariance of that fit -- for ONE frame.  The plane package's arithmetic is not in the reference; include/fgo.h states the
+// semantics this file implements, and tests/plane_extract_reference.py restates them in numpy.  The frames are independent:
+// fgo_plane_extract_batch runs ONE WORKGROUP (PX_WAVES waves) PER FRAME and all frames in one launch.
+//
+//   points   every pixel is back-projected once into the frame's scratch (3 doubles per pixel); its label starts as -2 (no depth)
+//            or -1 (free).
+//   compact  the candidates of a round (the free pixels) are written in pixel order by a workgroup prefix scan: a ballot and a
+//            population count inside a wave, the wave totals through LDS, PX_T pixels at a time.
+//   score    PX_HPL HYPOTHESES PER LANE, PX_PASS = PX_T PX_HPL a pass.  A lane draws its three candidates from the counter-based
+//            hash and builds (n, d).  The candidates are staged in LDS PX_CHUNK at a time (x, y as one 16-byte pair, z apart);
+//            every lane reads the same point at the same time (a broadcast read) and tests |n.p + d| <= max_dist for each of its
+//            hypotheses.  A dead hypothesis carries n = 0, d = huge and counts nothing, so the loop does not diverge; the barriers
+//            around the staging are outside every branch that is not uniform over the workgroup.
+//   winner   a lane keeps the best (count, h) of its own hypotheses (h rises, a later one has to be strictly better); the lanes are
+//            merged by an integer butterfly (larger count, then lower h), the waves through LDS in wave order.
+//   fit      the lanes stride the candidates (or the pixels): sums for the centroid, sums for the scatter of the centred points, the
+//            3x3 eigenproblem by PX_SWEEPS cyclic Jacobi sweeps (uniform over the workgroup, redundantly in every lane), the new
+//            set by the same distance function the scoring uses.
+//   final    every pixel with a depth goes to the nearest kept plane, planes left below min_pixels are dropped, every remaining
+//            plane is fitted once more; a last pass forms the two 3x3 sums of the sandwich covariance.
+// Every sum over pixels is a per-lane sum in pixel order followed by a butterfly whose result is bit-identical in every lane, and
+// the waves' sums are added in wave order by every lane: no atomics, no dependence on the rest of the batch, and every decision is
+// uniform over the workgroup without a broadcast.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <climits>
+#include <cmath>
+#include "../../include/fgo.h"
+
+namespace fgo {
+namespace {
+
+constexpr int PX_WAVES = 4;                      // waves of a workgroup
+constexpr int PX_T = 64 * PX_WAVES;
+constexpr int PX_HPL = 2;                        // hypotheses a lane scores at a time: one LDS read serves both
+constexpr int PX_PASS = PX_T * PX_HPL;           // hypotheses of one pass over the candidates
+constexpr int PX_CHUNK = 2048;                   // candidates staged in LDS at a time (48 KB)
+constexpr int PX_SWEEPS = 8;                     // cyclic Jacobi sweeps of the 3x3 eigenproblem (quadratic convergence: 4 - 5 reach rounding)
+constexpr int PX_MAX_PIXELS = 1 << 24;
+constexpr int PX_MAX_HYP = 1 << 16;
+constexpr int PX_NSUM = 13;                      // the widest block sum: rmse, A (6), M (6)
+
+struct PxArgs {
+  int64_t n;
+  int W, NP;
+  const uint16_t *depth;
+  double fx, fy, cx, cy, z_scale, z_min, z_max, max_dist, min_area, s_px2, sz0, sz1, sz2;
+  int K, min_pixels, max_planes, refine_rounds;
+  uint64_t seed;
+  double *pts;                                  // scratch: n x NP x 3
+  int32_t *cand;                                // scratch: n x NP, the candidates of the round in pixel order
+  uint8_t *inset;                               // scratch: n x NP, by candidate
+  int8_t *label;                                // n x NP: always there, the kernel works in it
+  double *abcd, *cov16, *ut6;                   // ut6 may be NULL
+  fgo_plane_extract_plane *plane;               // may be NULL
+  int32_t *hyp;                                 // may be NULL
+  fgo_plane_extract_result *res;
+};
+
+__device__ __forceinline__ double wsum(double v) {     // every lane ends with the same bits (each step adds the same two numbers on both sides)
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int wsum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// larger count first, then the lower hypothesis
+__device__ __forceinline__ void better(int &cnt, int &h, int cnt2, int h2) {
+  if (cnt2 > cnt || (cnt2 == cnt && h2 < h)) { cnt = cnt2; h = h2; }
+}
+
+// the sums of a workgroup: butterfly inside a wave, the waves in wave order; two barriers, the first lets the readers of the
+// previous sum finish.  Every thread of the workgroup has to call it.
+template <class T, int N>
+__device__ __forceinline__ void bsum(T (&v)[N], T *red) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int c = 0; c < N; ++c) v[c] = wsum(v[c]);
+  __syncthreads();
+  if (lane == 0) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) red[wave * N + c] = v[c];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < N; ++c) {
+    T t = red[c];
+#pragma unroll
+    for (int w = 1; w < PX_WAVES; ++w) t += red[w * N + c];
+    v[c] = t;
+  }
+}
+
+__device__ __forceinline__ uint64_t mix(uint64_t z) {
+  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27; z *= 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return z;
+}
+// the VRO sampler with the round folded into the counter: hc = r K + h
+__device__ __forceinline__ void sample3(uint64_t seed, uint64_t hc, int M, int &a, int &b, int &c) {
+  const uint64_t g = 0x9E3779B97F4A7C15ull, k0 = 3ull * hc + 1ull;
+  a = (int)(mix(seed + k0 * g) % (uint64_t)M);
+  b = (int)(mix(seed + (k0 + 1) * g) % (uint64_t)(M - 1));
+  b += b >= a;
+  c = (int)(mix(seed + (k0 + 2) * g) % (uint64_t)(M - 2));
+  c += c >= min(a, b);
+  c += c >= max(a, b);
+}
+
+struct Pl { double n[3], d; };
+
+// |n.p + d| with the roundings spelled out: the scoring, the refinement and the final pass have to agree on every point
+__device__ __forceinline__ double pdist(const Pl &P, double x, double y, double z) {
+  return fabs(fma(P.n[0], x, fma(P.n[1], y, fma(P.n[2], z, P.d))));
+}
+// the camera is on the positive side
+__device__ __forceinline__ void orient(Pl &P) {
+  if (P.d < 0) { P.n[0] = -P.n[0]; P.n[1] = -P.n[1]; P.n[2] = -P.n[2]; P.d = -P.d; }
+}
+
+// hypothesis hc = r K + h over the M >= 3 candidates; false if it is invalid
+__device__ __forceinline__ bool hypothesis(const PxArgs &A, const double *__restrict__ pts, const int32_t *__restrict__ cand, uint64_t hc, int M, Pl &P) {
+  int a, b, c;
+  sample3(A.seed, hc, M, a, b, c);
+  const double *pa = pts + 3 * (int64_t)cand[a], *pb = pts + 3 * (int64_t)cand[b], *pc = pts + 3 * (int64_t)cand[c];
+  const double a0 = pa[0], a1 = pa[1], a2 = pa[2];
+  const double e0 = pb[0] - a0, e1 = pb[1] - a1, e2 = pb[2] - a2, f0 = pc[0] - a0, f1 = pc[1] - a1, f2 = pc[2] - a2;
+  const double m0 = e1 * f2 - e2 * f1, m1 = e2 * f0 - e0 * f2, m2 = e0 * f1 - e1 * f0;
+  const double nm = sqrt(m0 * m0 + m1 * m1 + m2 * m2);
+  if (!(nm >= A.min_area)) return false;
+  P.n[0] = m0 / nm; P.n[1] = m1 / nm; P.n[2] = m2 / nm;
+  P.d = -(P.n[0] * a0 + P.n[1] * a1 + P.n[2] * a2);
+  orient(P);
+  return true;
+}
+
+// one cyclic Jacobi rotation on the symmetric 3x3 a (full storage) with the eigenvectors accumulated in the columns of v
+template <int P, int Q>
+__device__ __forceinline__ void jacobi_rot(double a[9], double v[9]) {
+  const double apq = a[3 * P + Q];
+  if (apq == 0.0) return;
+  const double theta = (a[3 * Q + Q] - a[3 * P + P]) / (2.0 * apq);
+  const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+  const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {                    // columns P, Q
+    const double akp = a[3 * k + P], akq = a[3 * k + Q];
+    a[3 * k + P] = c * akp - s * akq;
+    a[3 * k + Q] = s * akp + c * akq;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {                    // rows P, Q
+    const double apk = a[3 * P + k], aqk = a[3 * Q + k];
+    a[3 * P + k] = c * apk - s * aqk;
+    a[3 * Q + k] = s * apk + c * aqk;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double vkp = v[3 * k + P], vkq = v[3 * k + Q];
+    v[3 * k + P] = c * vkp - s * vkq;
+    v[3 * k + Q] = s * vkp + c * vkq;
+  }
+}
+
+// The total-least-squares plane of the points sel names among `count` slots (sel(i) = the pixel of slot i, or -1), by every thread
+// of the workgroup: the centroid, the scatter of the centred points (two passes), the eigenvector of the smallest eigenvalue.
+// N = the number of points.  N == 0 leaves non-finite values behind; the callers never fit an empty set.
+template <class Sel>
+__device__ __forceinline__ void fit_plane(const double *__restrict__ pts, int count, Sel sel, double *red, Pl &P, double cen[3], int &N) {
+  double s[4] = {0, 0, 0, 0};
+  for (int i = threadIdx.x; i < count; i += PX_T) {
+    const int pix = sel(i);
+    if (pix < 0) continue;
+    const double *p = pts + 3 * (int64_t)pix;
+    s[0] += p[0]; s[1] += p[1]; s[2] += p[2]; s[3] += 1.0;
+  }
+  bsum(s, red);
+  N = (int)s[3];                                  // exact: at most 2^24 ones
+#pragma unroll
+  for (int k = 0; k < 3; ++k) cen[k] = s[k] / s[3];
+  double q[6] = {0, 0, 0, 0, 0, 0};               // xx xy xz yy yz zz
+  for (int i = threadIdx.x; i < count; i += PX_T) {
+    const int pix = sel(i);
+    if (pix < 0) continue;
+    const double *p = pts + 3 * (int64_t)pix;
+    const double x = p[0] - cen[0], y = p[1] - cen[1], z = p[2] - cen[2];
+    q[0] += x * x; q[1] += x * y; q[2] += x * z; q[3] += y * y; q[4] += y * z; q[5] += z * z;
+  }
+  bsum(q, red);
+  double a[9] = {q[0], q[1], q[2], q[1], q[3], q[4], q[2], q[4], q[5]};
+  double v[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+#pragma unroll 1
+  for (int sweep = 0; sweep < PX_SWEEPS; ++sweep) {
+    jacobi_rot<0, 1>(a, v); jacobi_rot<0, 2>(a, v); jacobi_rot<1, 2>(a, v);
+  }
+  double least = a[0], e[3] = {v[0], v[3], v[6]};
+#pragma unroll
+  for (int k = 1; k < 3; ++k)
+    if (a[4 * k] < least) { least = a[4 * k]; e[0] = v[k]; e[1] = v[3 + k]; e[2] = v[6 + k]; }
+  const double nn = sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+  P.n[0] = e[0] / nn; P.n[1] = e[1] / nn; P.n[2] = e[2] / nn;
+  P.d = -(P.n[0] * cen[0] + P.n[1] * cen[1] + P.n[2] * cen[2]);
+  orient(P);
+}
+
+__device__ __forceinline__ bool pivot_ok(double d) { return d > 0 && d < __builtin_huge_val(); }
+__device__ __forceinline__ bool finite(double d) { return fabs(d) < __builtin_huge_val(); }
+
+__global__ __launch_bounds__(PX_T) void k_plane_extract(PxArgs A) {
+  __shared__ __attribute__((aligned(16))) double2 s_xy[PX_CHUNK];     // a chunk of candidates
+  __shared__ double s_z[PX_CHUNK];
+  __shared__ double red_d[PX_WAVES * PX_NSUM];
+  __shared__ int red_i[PX_WAVES * FGO_PX_MAX_PLANES];
+  __shared__ int w_n[PX_WAVES], w_cnt[PX_WAVES], w_h[PX_WAVES], w_valid[PX_WAVES];
+  __shared__ Pl pl[FGO_PX_MAX_PLANES];                                // the planes the rounds kept
+  __shared__ int pl_meta[FGO_PX_MAX_PLANES][4];                       // best_hypothesis, best_count, n_valid_hyp, fits
+  __shared__ int pl_map[FGO_PX_MAX_PLANES];                           // final pass: the new index of a kept plane, or -1
+  const int64_t frame = blockIdx.x;
+  if (frame >= A.n) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NP = A.NP, K = A.K;
+  const uint16_t *__restrict__ dep = A.depth + frame * NP;
+  double *__restrict__ pts = A.pts + 3 * frame * NP;
+  int32_t *__restrict__ cand = A.cand + frame * NP;
+  uint8_t *__restrict__ inset = A.inset + frame * NP;
+  int8_t *__restrict__ lab = A.label + frame * NP;
+  int32_t *__restrict__ hyp = A.hyp ? A.hyp + frame * (int64_t)A.max_planes * K : nullptr;
+  const double md = A.max_dist;
+
+  // ---- points
+  int nv[1] = {0};
+  for (int pix = tid; pix < NP; pix += PX_T) {
+    const int v = pix / A.W, u = pix - v * A.W;
+    const double z = (double)dep[pix] * A.z_scale;
+    const bool valid = z > A.z_min && z < A.z_max;
+    pts[3 * (int64_t)pix] = ((double)u - A.cx) * z / A.fx;
+    pts[3 * (int64_t)pix + 1] = ((double)v - A.cy) * z / A.fy;
+    pts[3 * (int64_t)pix + 2] = z;
+    lab[pix] = valid ? -1 : -2;
+    nv[0] += valid;
+  }
+  bsum(nv, red_i);                                 // its barriers publish pts and lab to the workgroup
+  const int n_valid_pixels = nv[0];
+
+  // ---- rounds: everything below that is not indexed by a pixel is uniform over the workgroup
+  int kept = 0, rounds_run = 0;
+  const int need = max(3, A.min_pixels);
+  for (int r = 0; r < A.max_planes; ++r) {
+    // compact the free pixels in pixel order
+    __syncthreads();                               // the labels and the plane of the round before are visible
+    int M = 0;
+    for (int base = 0; base < NP; base += PX_T) {
+      const int pix = base + tid;
+      const bool f = pix < NP && lab[pix] == -1;
+      const unsigned long long bal = __ballot(f);
+      __syncthreads();                             // the readers of w_n of the tile before are done
+      if (lane == 0) w_n[wave] = __popcll(bal);
+      __syncthreads();
+      int off = M;
+#pragma unroll
+      for (int w = 0; w < PX_WAVES; ++w) {
+        const int c = w_n[w];
+        off += w < wave ? c : 0;
+        M += c;
+      }
+      if (f) cand[off + __popcll(bal & ((1ull << lane) - 1ull))] = pix;
+    }
+    __syncthreads();                               // cand is complete
+    if (M < need) break;
+    ++rounds_run;
+
+    // score
+    int my_cnt = -1, my_h = INT_MAX, my_valid = 0;
+    const int passes = (K + PX_PASS - 1) / PX_PASS, chunks = (M + PX_CHUNK - 1) / PX_CHUNK;
+    for (int pass = 0; pass < passes; ++pass) {
+      Pl H[PX_HPL];
+      bool live[PX_HPL];
+      int cnt[PX_HPL];
+#pragma unroll
+      for (int j = 0; j < PX_HPL; ++j) {
+        const int h = pass * PX_PASS + j * PX_T + tid;
+        live[j] = h < K && hypothesis(A, pts, cand, (uint64_t)r * (uint64_t)K + (uint64_t)h, M, H[j]);
+        if (!live[j]) { H[j].n[0] = H[j].n[1] = H[j].n[2] = 0; H[j].d = 1e300; }
+        cnt[j] = 0;
+      }
+      bool any = false;
+#pragma unroll
+      for (int j = 0; j < PX_HPL; ++j) any = any || live[j];
+      for (int ch = 0; ch < chunks; ++ch) {
+        const int m0 = ch * PX_CHUNK, mc = min(PX_CHUNK, M - m0);
+        if (chunks > 1 || pass == 0) {             // uniform: a round of one chunk is staged once
+          __syncthreads();
+          for (int e = tid; e < mc; e += PX_T) {
+            const double *p = pts + 3 * (int64_t)cand[m0 + e];
+            s_xy[e] = make_double2(p[0], p[1]);
+            s_z[e] = p[2];
+          }
+          __syncthreads();
+        }
+        if (any) {
+#pragma unroll 8
+          for (int m = 0; m < mc; ++m) {            // unrolled: the LDS reads of eight points are in flight at once
+            const double2 xy = s_xy[m];
+            const double z = s_z[m];
+#pragma unroll
+            for (int j = 0; j < PX_HPL; ++j) cnt[j] += pdist(H[j], xy.x, xy.y, z) <= md;
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < PX_HPL; ++j) {
+        const int h = pass * PX_PASS + j * PX_T + tid;
+        if (h < K) {
+          const int c = live[j] ? cnt[j] : -1;
+          if (hyp) hyp[(int64_t)r * K + h] = c;
+          my_valid += live[j];
+          if (c > my_cnt) { my_cnt = c; my_h = h; }
+        }
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) better(my_cnt, my_h, __shfl_xor(my_cnt, o, 64), __shfl_xor(my_h, o, 64));
+    my_valid = wsum(my_valid);
+    __syncthreads();                               // the readers of the round before are done
+    if (lane == 0) { w_cnt[wave] = my_cnt; w_h[wave] = my_h; w_valid[wave] = my_valid; }
+    __syncthreads();
+    int best_cnt = w_cnt[0], best_h = w_h[0], n_valid = w_valid[0];
+#pragma unroll
+    for (int w = 1; w < PX_WAVES; ++w) { better(best_cnt, best_h, w_cnt[w], w_h[w]); n_valid += w_valid[w]; }
+    if (best_cnt < 0 || best_cnt < A.min_pixels) break;
+
+    // refine: the set starts as the winner's inliers; a thread owns the candidates tid, tid + PX_T, ...
+    Pl P;
+    hypothesis(A, pts, cand, (uint64_t)r * (uint64_t)K + (uint64_t)best_h, M, P);
+    for (int i = tid; i < M; i += PX_T) {
+      const double *p = pts + 3 * (int64_t)cand[i];
+      inset[i] = pdist(P, p[0], p[1], p[2]) <= md;
+    }
+    int fits = 0;
+    bool keep = true;
+    for (int round = 0; round < A.refine_rounds; ++round) {
+      double cen[3];
+      int N;
+      fit_plane(pts, M, [&](int i) { return inset[i] ? cand[i] : -1; }, red_d, P, cen, N);
+      ++fits;
+      int chg[2] = {0, 0};                         // changed, members
+      for (int i = tid; i < M; i += PX_T) {
+        const double *p = pts + 3 * (int64_t)cand[i];
+        const bool in = pdist(P, p[0], p[1], p[2]) <= md;
+        chg[0] += in != (inset[i] != 0);
+        chg[1] += in;
+        inset[i] = in;
+      }
+      bsum(chg, red_i);
+      if (chg[1] < A.min_pixels) { keep = false; break; }
+      if (chg[0] == 0) break;
+    }
+    if (!keep) break;
+    for (int i = tid; i < M; i += PX_T)
+      if (inset[i]) lab[cand[i]] = (int8_t)r;
+    if (tid == 0) {
+      pl[kept] = P;
+      pl_meta[kept][0] = best_h; pl_meta[kept][1] = best_cnt; pl_meta[kept][2] = n_valid; pl_meta[kept][3] = fits;
+    }
+    ++kept;
+  }
+  __syncthreads();
+
+  // ---- final pass: every pixel with a depth goes to the nearest kept plane (ties to the lower index)
+  int cntk[FGO_PX_MAX_PLANES];
+#pragma unroll
+  for (int k = 0; k < FGO_PX_MAX_PLANES; ++k) cntk[k] = 0;
+  for (int pix = tid; pix < NP; pix += PX_T) {
+    if (lab[pix] == -2) continue;
+    const double *p = pts + 3 * (int64_t)pix;
+    const double x = p[0], y = p[1], z = p[2];
+    int best = -1;
+    double bd = __builtin_huge_val();
+    for (int k = 0; k < kept; ++k) {
+      const double d = pdist(pl[k], x, y, z);
+      if (d < bd) { bd = d; best = k; }
+    }
+    if (!(bd <= md)) best = -1;
+    lab[pix] = (int8_t)best;
+#pragma unroll
+    for (int k = 0; k < FGO_PX_MAX_PLANES; ++k) cntk[k] += best == k;
+  }
+  bsum(cntk, red_i);
+  int n_planes = 0;
+#pragma unroll
+  for (int k = 0; k < FGO_PX_MAX_PLANES; ++k) {
+    const bool stays = k < kept && cntk[k] >= A.min_pixels;
+    if (tid == 0) pl_map[k] = stays ? n_planes : -1;
+    n_planes += stays;
+  }
+  __syncthreads();
+  if (n_planes != kept) {
+    for (int pix = tid; pix < NP; pix += PX_T) {
+      const int l = lab[pix];
+      if (l >= 0) lab[pix] = (int8_t)pl_map[l];
+    }
+  }
+  __syncthreads();
+
+  // ---- the final fit of every remaining plane, and the covariance of that fit
+  int status = FGO_PX_OK;
+  double *abcd = A.abcd + frame * A.max_planes * 4, *cov16 = A.cov16 + frame * A.max_planes * 16;
+  double *ut6 = A.ut6 ? A.ut6 + frame * A.max_planes * 6 : nullptr;
+  fgo_plane_extract_plane *po = A.plane ? A.plane + frame * A.max_planes : nullptr;
+  int old = 0;
+  for (int k = 0; k < n_planes; ++k, ++old) {
+    while (pl_map[old] < 0) ++old;                 // the round's slot this plane came from
+    Pl P;
+    double cen[3];
+    int N;
+    fit_plane(pts, NP, [&](int pix) { return lab[pix] == k ? pix : -1; }, red_d, P, cen, N);
+    // B = Unit3::basis(n): b1 = normalise(n x the axis of the smallest |n_i|), b2 = n x b1 (ties: x, then y, then z)
+    const double mx = fabs(P.n[0]), my = fabs(P.n[1]), mz = fabs(P.n[2]);
+    double ax[3] = {0, 0, 1};
+    if (mx <= my && mx <= mz) { ax[0] = 1; ax[2] = 0; }
+    else if (my <= mx && my <= mz) { ax[1] = 1; ax[2] = 0; }
+    double b1[3] = {P.n[1] * ax[2] - P.n[2] * ax[1], P.n[2] * ax[0] - P.n[0] * ax[2], P.n[0] * ax[1] - P.n[1] * ax[0]};
+    const double nb = sqrt(b1[0] * b1[0] + b1[1] * b1[1] + b1[2] * b1[2]);
+    b1[0] /= nb; b1[1] /= nb; b1[2] /= nb;
+    const double b2[3] = {P.n[1] * b1[2] - P.n[2] * b1[1], P.n[2] * b1[0] - P.n[0] * b1[2], P.n[0] * b1[1] - P.n[1] * b1[0]};
+    // J = [p^T B, 1], sigma^2 = n^T Sigma(p) n: ss, A = sum J^T J (a00 a01 a02 a11 a12 a22), M = sum sigma^2 J^T J
+    double s[PX_NSUM];
+#pragma unroll
+    for (int c = 0; c < PX_NSUM; ++c) s[c] = 0;
+    for (int pix = tid; pix < NP; pix += PX_T) {
+      if (lab[pix] != k) continue;
+      const double *p = pts + 3 * (int64_t)pix;
+      const double x = p[0], y = p[1], z = p[2];
+      const double e = fma(P.n[0], x, fma(P.n[1], y, fma(P.n[2], z, P.d)));
+      const double j0 = b1[0] * x + b1[1] * y + b1[2] * z, j1 = b2[0] * x + b2[1] * y + b2[2] * z;
+      const double sz = A.sz0 + z * (A.sz1 + z * A.sz2), gx = P.n[0] * z / A.fx, gy = P.n[1] * z / A.fy;
+      const double nr = P.n[0] * (x / z) + P.n[1] * (y / z) + P.n[2];
+      const double v = A.s_px2 * (gx * gx + gy * gy) + sz * sz * nr * nr;
+      s[0] += e * e;
+      s[1] += j0 * j0; s[2] += j0 * j1; s[3] += j0; s[4] += j1 * j1; s[5] += j1; s[6] += 1.0;
+      s[7] += v * j0 * j0; s[8] += v * j0 * j1; s[9] += v * j0; s[10] += v * j1 * j1; s[11] += v * j1; s[12] += v;
+    }
+    bsum(s, red_d);
+    const double rmse = sqrt(s[0] / (double)N);
+    // A = L L^T, Ai = A^-1 = L^-T L^-1
+    const bool ok0 = pivot_ok(s[1]);
+    const double l00 = sqrt(ok0 ? s[1] : 1.0), l10 = s[2] / l00, l20 = s[3] / l00;
+    const double d1 = s[4] - l10 * l10;
+    const bool ok1 = pivot_ok(d1);
+    const double l11 = sqrt(ok1 ? d1 : 1.0), l21 = (s[5] - l20 * l10) / l11;
+    const double d2 = s[6] - l20 * l20 - l21 * l21;
+    const bool ok2 = pivot_ok(d2);
+    const double l22 = sqrt(ok2 ? d2 : 1.0);
+    const double i00 = 1.0 / l00, i11 = 1.0 / l11, i22 = 1.0 / l22;
+    const double i10 = -l10 * i00 * i11, i21 = -l21 * i11 * i22, i20 = -(l20 * i00 + l21 * i10) * i22;     // L^-1, lower
+    double Ai[9];
+    Ai[0] = i00 * i00 + i10 * i10 + i20 * i20; Ai[1] = i10 * i11 + i20 * i21; Ai[2] = i20 * i22;
+    Ai[4] = i11 * i11 + i21 * i21; Ai[5] = i21 * i22; Ai[8] = i22 * i22;
+    Ai[3] = Ai[1]; Ai[6] = Ai[2]; Ai[7] = Ai[5];
+    const double Mm[9] = {s[7], s[8], s[9], s[8], s[10], s[11], s[9], s[11], s[12]};
+    double T[9], C[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) T[3 * r + c] = Ai[3 * r] * Mm[c] + Ai[3 * r + 1] * Mm[3 + c] + Ai[3 * r + 2] * Mm[6 + c];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = r; c < 3; ++c) {
+        C[3 * r + c] = T[3 * r] * Ai[c] + T[3 * r + 1] * Ai[3 + c] + T[3 * r + 2] * Ai[6 + c];
+        C[3 * c + r] = C[3 * r + c];
+      }
+    double chk = P.n[0] + P.n[1] + P.n[2] + P.d + cen[0] + cen[1] + cen[2] + rmse;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) chk += C[c];
+    if (!(ok0 && ok1 && ok2) || !finite(chk)) { status = FGO_PX_NUM; break; }
+    if (tid == 0) {
+      abcd[4 * k] = P.n[0]; abcd[4 * k + 1] = P.n[1]; abcd[4 * k + 2] = P.n[2]; abcd[4 * k + 3] = P.d;
+      // cov16 = E C E^T, E = [[B, 0], [0, 1]]
+      const double Bm[6] = {b1[0], b2[0], b1[1], b2[1], b1[2], b2[2]};     // 3x2, row-major
+      double *o = cov16 + 16 * k;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const double t0 = Bm[2 * r] * C[0] + Bm[2 * r + 1] * C[3], t1 = Bm[2 * r] * C[1] + Bm[2 * r + 1] * C[4];
+#pragma unroll
+        for (int c = r; c < 3; ++c) {
+          o[4 * r + c] = t0 * Bm[2 * c] + t1 * Bm[2 * c + 1];
+          o[4 * c + r] = o[4 * r + c];
+        }
+        o[4 * r + 3] = Bm[2 * r] * C[2] + Bm[2 * r + 1] * C[5];
+        o[12 + r] = o[4 * r + 3];
+      }
+      o[15] = C[8];
+      if (ut6) { double *u = ut6 + 6 * k; u[0] = C[0]; u[1] = C[1]; u[2] = C[2]; u[3] = C[4]; u[4] = C[5]; u[5] = C[8]; }
+      if (po) po[k] = {N, pl_meta[old][0], pl_meta[old][1], pl_meta[old][2], pl_meta[old][3], 0, rmse, {cen[0], cen[1], cen[2]}};
+    }
+  }
+
+  // ---- a frame that failed numerically has no planes: zero outputs, labels of -2 / -1 only
+  if (status != FGO_PX_OK) {
+    __syncthreads();                               // thread 0's writes of the planes before the failing one
+    for (int pix = tid; pix < NP; pix += PX_T)
+      if (lab[pix] >= 0) lab[pix] = -1;
+    for (int e = tid; e < 4 * A.max_planes; e += PX_T) abcd[e] = 0;
+    for (int e = tid; e < 16 * A.max_planes; e += PX_T) cov16[e] = 0;
+    if (ut6)
+      for (int e = tid; e < 6 * A.max_planes; e += PX_T) ut6[e] = 0;
+    if (po)
+      for (int e = tid; e < A.max_planes; e += PX_T) po[e] = {0, 0, 0, 0, 0, 0, 0.0, {0.0, 0.0, 0.0}};
+    n_planes = 0;
+  }
+  if (hyp)
+    for (int e = rounds_run * K + tid; e < A.max_planes * K; e += PX_T) hyp[e] = -2;
+  if (tid == 0) A.res[frame] = {status, n_planes, n_valid_pixels, rounds_run};
+}
+
+// Every device array of a call lives in ONE allocation: a call costs one hipMalloc / hipFree whatever it asks for.  reserve() hands
+// out offsets (256-byte aligned) before the allocation is made, at() turns them into pointers afterwards.
+struct Arena {
+  char *base = nullptr;
+  size_t total = 0;
+  ~Arena() { if (base) (void)hipFree(base); }
+  size_t reserve(size_t bytes) { const size_t o = total; total += (bytes + 255) & ~(size_t)255; return o; }
+  hipError_t alloc() { return hipMalloc((void **)&base, total ? total : 1); }
+  template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(base + off); }
+};
+struct Events {
+  hipEvent_t a = nullptr, b = nullptr;
+  ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+};
+
+double g_kernel_ms = 0.0;
+
+}  // namespace
+}  // namespace fgo
+
+extern "C" double fgo_debug_plane_extract_kernel_ms(void) { return fgo::g_kernel_ms; }
+
+extern "C" void fgo_plane_extract_params_default(fgo_plane_extract_params *p) {
+  if (!p) return;
+  p->fx = p->fy = 250.5773;
+  p->cx = 90.0; p->cy = 70.0;
+  p->z_scale = 0.001;
+  p->z_min = 0.1; p->z_max = 5.0;
+  p->hypotheses = 512;
+  p->seed = 0;
+  p->max_dist = 0.05;
+  p->min_area = 1e-3;
+  p->min_pixels = 1500;
+  p->max_planes = 4;
+  p->refine_rounds = 3;
+  p->sigma_px = 1.0;
+  p->sigma_z[0] = 0.014; p->sigma_z[1] = 0.0; p->sigma_z[2] = 0.0;
+}
+
+extern "C" int fgo_plane_extract_batch(int device, int64_t n_frames, int width, int height, const uint16_t *depth,
+                                       const fgo_plane_extract_params *params, fgo_plane_extract_result *result, double *abcd_out,
+                                       double *cov16_out, double *cov_ut6_out, fgo_plane_extract_plane *plane_out, int8_t *label_out,
+                                       int32_t *hyp_count_out) {
+  using namespace fgo;
+  fgo_plane_extract_params P;
+  fgo_plane_extract_params_default(&P);
+  if (params) P = *params;
+  if (n_frames < 0 || n_frames > INT_MAX) return FGO_EINVAL;
+  if (width < 1 || height < 1 || (int64_t)width * height > PX_MAX_PIXELS) return FGO_EINVAL;
+  if (!(P.fx > 0) || !(P.fy > 0) || !(P.z_scale > 0) || !(P.max_dist > 0) || !(P.min_area > 0) || !(P.sigma_px > 0)) return FGO_EINVAL;
+  if (!(P.z_min < P.z_max) || !(fabs(P.cx) < HUGE_VAL) || !(fabs(P.cy) < HUGE_VAL)) return FGO_EINVAL;
+  if (P.hypotheses < 1 || P.hypotheses > PX_MAX_HYP || P.max_planes < 1 || P.max_planes > FGO_PX_MAX_PLANES || P.refine_rounds < 0 ||
+      P.refine_rounds > 10 || P.min_pixels < 3)
+    return FGO_EINVAL;
+  if (!(P.sigma_z[0] >= 0) || !(P.sigma_z[1] >= 0) || !(P.sigma_z[2] >= 0) || !(P.sigma_z[0] + P.sigma_z[1] + P.sigma_z[2] > 0)) return FGO_EINVAL;
+  if (n_frames == 0) return FGO_OK;
+  if (!depth || !result || !abcd_out || !cov16_out) return FGO_EINVAL;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FGO_ENODEV;   // no CPU fallback
+  if (hipSetDevice(device) != hipSuccess) return FGO_ENODEV;
+  const size_t n = (size_t)n_frames, np = (size_t)width * (size_t)height, D = sizeof(double), K = (size_t)P.hypotheses, mp = (size_t)P.max_planes;
+  Arena M;
+  const size_t in_off = M.reserve(n * np * sizeof(uint16_t));
+  // scratch: the points, the candidates and the set; then the outputs (the labels are always there: the kernel works in them)
+  const size_t pts_off = M.reserve(3 * n * np * D), cand_off = M.reserve(n * np * sizeof(int32_t)), set_off = M.reserve(n * np);
+  void *out_host[7] = {result, abcd_out, cov16_out, cov_ut6_out, plane_out, label_out, hyp_count_out};
+  const size_t out_bytes[7] = {n * sizeof(fgo_plane_extract_result), 4 * n * mp * D, 16 * n * mp * D, 6 * n * mp * D,
+                               n * mp * sizeof(fgo_plane_extract_plane), n * np, n * mp * K * sizeof(int32_t)};
+  size_t out_off[7];
+  for (int k = 0; k < 7; ++k) out_off[k] = (out_host[k] || k == 5) ? M.reserve(out_bytes[k]) : 0;
+  if (M.alloc() != hipSuccess) return FGO_ENOMEM;
+  if (hipMemcpy(M.at<char>(in_off), depth, n * np * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess) return FGO_ENUM;
+  for (int k = 1; k <= 4; ++k)                                  // the slots past a frame's last plane stay zero
+    if (out_host[k] && hipMemset(M.at<char>(out_off[k]), 0, out_bytes[k]) != hipSuccess) return FGO_ENUM;
+  PxArgs A;
+  A.n = n_frames; A.W = width; A.NP = (int)np;
+  A.depth = M.at<uint16_t>(in_off);
+  A.fx = P.fx; A.fy = P.fy; A.cx = P.cx; A.cy = P.cy; A.z_scale = P.z_scale; A.z_min = P.z_min; A.z_max = P.z_max;
+  A.max_dist = P.max_dist; A.min_area = P.min_area; A.s_px2 = P.sigma_px * P.sigma_px;
+  A.sz0 = P.sigma_z[0]; A.sz1 = P.sigma_z[1]; A.sz2 = P.sigma_z[2];
+  A.K = P.hypotheses; A.min_pixels = P.min_pixels; A.max_planes = P.max_planes; A.refine_rounds = P.refine_rounds;
+  A.seed = P.seed;
+  A.pts = M.at<double>(pts_off); A.cand = M.at<int32_t>(cand_off); A.inset = M.at<uint8_t>(set_off);
+  A.res = M.at<fgo_plane_extract_result>(out_off[0]);
+  A.abcd = M.at<double>(out_off[1]); A.cov16 = M.at<double>(out_off[2]);
+  A.ut6 = cov_ut6_out ? M.at<double>(out_off[3]) : nullptr;
+  A.plane = plane_out ? M.at<fgo_plane_extract_plane>(out_off[4]) : nullptr;
+  A.label = M.at<int8_t>(out_off[5]);
+  A.hyp = hyp_count_out ? M.at<int32_t>(out_off[6]) : nullptr;
+  Events ev;
+  if (hipEventCreate(&ev.a) != hipSuccess || hipEventCreate(&ev.b) != hipSuccess) return FGO_ENUM;
+  (void)hipEventRecord(ev.a, 0);
+  hipLaunchKernelGGL(k_plane_extract, dim3((unsigned)n_frames), dim3(PX_T), 0, 0, A);
+  (void)hipEventRecord(ev.b, 0);
+  if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return FGO_ENUM;
+  float ms = 0;
+  g_kernel_ms = hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess ? (double)ms : 0.0;
+  for (int k = 0; k < 7; ++k)
+    if (out_host[k] && out_bytes[k] && hipMemcpy(out_host[k], M.at<char>(out_off[k]), out_bytes[k], hipMemcpyDeviceToHost) != hipSuccess)
+      return FGO_ENUM;
+  return FGO_OK;
+}

@@ -215,6 +215,85 @@ int fgo_plane_check_vro_batch(int device, int64_t n_records,
                               int64_t *match_out /* Mi */, double *d2_out /* Mi */, double *raw_out /* Mi */,
                               double *pred_abcd_out /* Mi x 4 */, double *pred_cov9_out /* Mi x 9 */,
                               double *sdj_out /* Mi */);   /* each of the six may be NULL */
+/* Plane extraction from depth frames, batched: the step that PRODUCES the planes the call above and fgo_add_plane_factor /
+ * fgo_gate_plane_factors / fgo_associate_planes consume -- what the reference obtains frame after frame, on the CPU, from
+ * CPlaneNode::extractPlanes(i_img, d_img, &sr4k) (gtsam/test_plane_check_vo.cpp:181,188,213; gtsam/test_ba_imu_graph.cpp:137,274,297;
+ * gtsam/test/test_plane_propagate.cpp:144,307) -- for n_frames independent frames in ONE launch, one workgroup per frame.  The plane
+ * package's own arithmetic is not part of the reference tree, so the semantics below are THIS PROJECT'S DEFINITION, pinned to the
+ * numpy restatement tests/plane_extract_reference.py and not to the plane package.  depth is n x H x W depth words, row-major.
+ *   points      pixel (u, v) with depth word w has z = w z_scale and is VALID iff z_min < z < z_max;
+ *               p = ((u - cx) z / fx, (v - cy) z / fy, z)  (CamModel::convertUVZ2XYZ; lens distortion is out of scope)
+ *   rounds      r = 0 .. max_planes - 1.  The CANDIDATES of round r are the valid pixels not yet given to a plane, in pixel order
+ *               (v W + u), M their number.  M < max(3, min_pixels): the search stops (the round is not run).
+ *   sampling    the sampler of fgo_vro_ransac_batch with the round folded into the counter: hypothesis h of round r draws
+ *               u_k = mix(seed + ((r hypotheses + h) 3 + k + 1) 0x9E3779B97F4A7C15), k = 0, 1, 2, and from them three distinct
+ *               candidates a, b, c exactly as there.  A hypothesis depends on (seed, r, h, M) only.
+ *   hypothesis  m = (p_b - p_a) x (p_c - p_a); invalid (count -1) if |m| < min_area.  n = m / |m|, d = -n.p_a, both negated when
+ *               d < 0: n.p + d = 0 with the camera on the positive side.  count = the number of candidates with |n.p + d| <= max_dist.
+ *               Winner: the largest count, ties to the lowest h.  No valid hypothesis, or the winner's count < min_pixels: the
+ *               search stops.
+ *   refinement  the set starts as the winner's inliers; up to refine_rounds times: total-least-squares fit on the set (centroid c,
+ *               the 3x3 scatter of the centred points in a second pass, the eigenvector of its smallest eigenvalue by a fixed
+ *               number of cyclic Jacobi sweeps, d = -n.c, the same orientation rule), the new set = the round's candidates within
+ *               max_dist of that fit; stop early when the set did not change.  A set below min_pixels: the search stops and this
+ *               plane is not kept.  Otherwise the set leaves the candidates and the next round begins.
+ *   final pass  every valid pixel goes to the kept plane with the smallest |n.p + d| (ties to the lower index) if that distance is
+ *               <= max_dist, else its label is -1.  A plane left with fewer than min_pixels is dropped: its pixels become -1 and the
+ *               later planes move up.  Each remaining plane is fitted once more on its final set by the same fit: that is abcd_out;
+ *               n_pixels, rmse (of n.p + d) and centroid are over that set.  The labels are not recomputed after the final fit.
+ *               Without this pass the first plane of a corner keeps the neighbouring walls' pixels within max_dist of it, and the
+ *               covariance below is too small by one to two orders of magnitude.
+ *   covariance  B = Unit3::basis(n), J_k = [p_k^T B, 1] (1x3), sigma_k^2 = n^T Sigma(p_k) n with Sigma(p) the pixel-plus-depth model
+ *               of fgo_vro_ransac_batch: sigma_px^2 ((n_x z / fx)^2 + (n_y z / fy)^2) + sigma_z(z)^2 (n.r)^2, r = p / z.  The fit
+ *               is unweighted, so its first-order covariance is the sandwich C = A^-1 M A^-1, A = sum J_k^T J_k (inverted by a
+ *               3x3 Cholesky), M = sum sigma_k^2 J_k^T J_k; C is exactly symmetric.  cov_ut6_out = the upper triangle of C in the
+ *               tangent [dn(2); dd]: what fgo_add_plane_factor, fgo_gate_plane_factors and fgo_associate_planes take.
+ *               cov16_out = E C E^T, E = [[B, 0], [0, 1]] (4x4 row-major): CPlane::m_CP as fgo_plane_check_vro_batch reads it (its
+ *               B^T S_n B and S_d return the diagonal blocks of C).  C is the covariance of the DEPTH NOISE, not of the
+ *               segmentation: near intersections a residual bias of the sequential search remains.
+ *   status      A not positive definite, or a non-finite value in a plane: the frame is FGO_PX_NUM with n_planes = 0, zero outputs
+ *               and labels of -2 / -1 only.  FGO_PX_OK otherwise; zero planes is OK.  rounds_run = the rounds whose hypotheses
+ *               were scored.  Per plane: best_hypothesis / best_count / n_valid_hyp of the round that found it, fits = the fits
+ *               of that round's refinement.  The slots past n_planes are zero.
+ *   diagnosis   hyp_count_out[f][r][h] = the count, -1 for an invalid hypothesis, -2 for every h of a round that was not run.
+ * Every sum over pixels is a per-lane sum in pixel order followed by a fixed butterfly, the waves merged in wave order, no atomics:
+ * results are bit-identical from call to call and do not depend on the rest of the batch.  Stateless, host arrays in and out, like
+ * fgo_vro_ransac_batch; the call holds 30 bytes of scratch per pixel of the batch on the device (FGO_ENOMEM: split the batch).
+ * FGO_EINVAL (before any HIP call): a NULL required pointer, a negative n_frames, width or height < 1 or width height > 2^24,
+ * fx / fy / z_scale / max_dist / min_area / sigma_px <= 0, z_min >= z_max, hypotheses outside [1, 65536], max_planes outside
+ * [1, FGO_PX_MAX_PLANES], refine_rounds outside [0, 10], min_pixels < 3, a sigma_z coefficient < 0 or all three zero;
+ * FGO_ENODEV without a HIP device (no CPU fallback).  n_frames == 0: FGO_OK. */
+#define FGO_PX_MAX_PLANES 8
+typedef struct {
+  double fx, fy, cx, cy;   /* 250.5773, 250.5773, 90, 70  (gtsam_graph.cpp:544) */
+  double z_scale;          /* 0.001: metres per depth word (CamModel::m_z_scale) */
+  double z_min, z_max;     /* 0.1, 5.0 */
+  int hypotheses;          /* 512, in [1, 65536]: per round */
+  uint64_t seed;           /* 0 */
+  double max_dist;         /* 0.05 m (our choice: about 3.5 sigma_z) */
+  double min_area;         /* 1e-3 m^2 */
+  int min_pixels;          /* 1500, >= 3 */
+  int max_planes;          /* 4, in [1, FGO_PX_MAX_PLANES] */
+  int refine_rounds;       /* 3, in [0, 10] */
+  double sigma_px;         /* 1.0 */
+  double sigma_z[3];       /* {0.014, 0, 0}: sigma_z(z) = s0 + s1 z + s2 z^2, as fgo_vro_params */
+} fgo_plane_extract_params;
+void fgo_plane_extract_params_default(fgo_plane_extract_params *p);      /* NULL tolerated */
+#define FGO_PX_OK 0
+#define FGO_PX_NUM 2       /* A is not positive definite or a plane holds a non-finite value: no planes, zero outputs */
+typedef struct { int status, n_planes, n_valid_pixels, rounds_run; } fgo_plane_extract_result;
+typedef struct { int n_pixels, best_hypothesis, best_count, n_valid_hyp, fits, reserved; double rmse, centroid[3]; } fgo_plane_extract_plane;
+int fgo_plane_extract_batch(int device, int64_t n_frames, int width, int height,
+                            const uint16_t *depth /* n x H x W, row-major */,
+                            const fgo_plane_extract_params *params /* NULL = defaults */,
+                            fgo_plane_extract_result *result /* n */,
+                            double *abcd_out /* n x max_planes x 4 */, double *cov16_out /* n x max_planes x 16 */,
+                            double *cov_ut6_out /* n x max_planes x 6, may be NULL */,
+                            fgo_plane_extract_plane *plane_out /* n x max_planes, may be NULL */,
+                            int8_t *label_out /* n x H x W, may be NULL: -2 no depth, -1 no plane, k */,
+                            int32_t *hyp_count_out /* n x max_planes x hypotheses, may be NULL: for tests and diagnosis */);
+/* development: the kernel time of the last fgo_plane_extract_batch call by HIP events, ms */
+double fgo_debug_plane_extract_kernel_ms(void);
 /* utils::chi2(dof, alpha) = boost::math::quantile(chi_squared(dof), alpha) (gtsam/chi2.h:17-26): the x with P(dof / 2, x / 2) = p, P the
  * regularised lower incomplete gamma function (series below x = a + 1, continued fraction above), inverted by a safeguarded Newton
  * iteration from the Wilson-Hilferty start.  Host only.  dof < 1: 0 (as the reference returns); p <= 0: 0; p >= 1: +inf; p NaN: NaN. */
