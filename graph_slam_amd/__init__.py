@@ -190,6 +190,9 @@ def _load():
     lib.fgo_debug_allreduce.argtypes = [C.c_void_p, dp, C.c_int64]
     lib.fgo_debug_read_system.argtypes = [C.c_void_p, dp, dp, dp]
     lib.fgo_debug_read_reduced.argtypes = [C.c_void_p, C.c_double, dp, dp, i64p]
+    lib.fgo_debug_solve_fused.argtypes = [C.c_void_p, C.c_double, dp]
+    lib.fgo_debug_launch_census.argtypes = [C.c_void_p, C.c_int, i64p, i64p, i64p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                            C.POINTER(C.c_int), C.c_char_p, C.c_int]
     lib.fgo_imu_params_vn100.argtypes = [dp]
     lib.fgo_preint_reset.argtypes = [dp, dp]
     lib.fgo_preint_integrate.argtypes = [dp, dp, dp, dp, C.c_double]
@@ -959,6 +962,29 @@ class Graph:
         d = np.zeros(6 * nf.value)
         self._chk(lib.fgo_solve_step(self._h, lam, _dp(d)))
         return d
+
+    def solve_fused(self, lam):
+        """the damped solve as an LM trial runs it: forward solve fused into the factor sweep (fgo_debug_solve_fused)"""
+        chi = C.c_double(); nf = C.c_int64()
+        self._chk(lib.fgo_linearize(self._h, C.byref(chi), None, None, C.byref(nf)))
+        d = np.zeros(6 * nf.value)
+        self._chk(lib.fgo_debug_solve_fused(self._h, lam, _dp(d)))
+        return d
+
+    def launch_census(self, fused=True):
+        """what one factor + solve launches (fgo_debug_launch_census; nothing runs): dict with 'forms' {instantiation:
+        (launches, workgroups, work items)}, 'level_riders', 'level_long' (per schedule level), 'chain_on', 'chain_mode'"""
+        ip = C.POINTER(C.c_int)
+        names = C.create_string_buffer(4096)
+        n = self._chk(lib.fgo_debug_launch_census(self._h, int(fused), None, None, None, 0, None, None, 0, None, names, len(names)))
+        nl = int(self.stats().n_levels)
+        la = np.zeros(n, np.int64); wg = np.zeros(n, np.int64); it = np.zeros(n, np.int64)
+        lr = np.zeros(max(nl, 1), np.int32); ll = np.zeros(max(nl, 1), np.int32); ch = np.zeros(2, np.int32)
+        self._chk(lib.fgo_debug_launch_census(self._h, int(fused), _i64p(la), _i64p(wg), _i64p(it), n, lr.ctypes.data_as(ip), ll.ctypes.data_as(ip), nl,
+                                              ch.ctypes.data_as(ip), None, 0))
+        keys = names.value.decode().split("\n")[:n]
+        return dict(forms={k: (int(a), int(w), int(i)) for k, a, w, i in zip(keys, la, wg, it)}, level_riders=[int(v) for v in lr[:nl]],
+                    level_long=[int(v) for v in ll[:nl]], chain_on=bool(ch[0]), chain_mode=int(ch[1]))
 
     def bench_phase(self, phase, reps):
         ms = C.c_double()

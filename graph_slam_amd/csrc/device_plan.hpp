@@ -275,13 +275,48 @@ struct PartialSweep {
   const int *g0, *g1, *c0, *c1;
   const int *task_ptr;
 };
+// ---- launch selection.  Which instantiation a level runs is decided by pure host functions of the schedule (select_*, kernels.hip);
+// the launchers switch on the enumerator they return, and a census (fgo_debug_launch_census) walks the same launchers with the
+// launches switched off, so tests can assert which form a threshold sends a level to.  The thresholds live in select_* only.
+enum LaunchForm {
+  LF_ACC8 = 0, LF_ACC4, LF_ACC2, LF_ACC1,            // k_chol_acc<SPLIT>
+  LF_ACC2_8, LF_ACC2_4, LF_ACC2_1,                   // k_chol_acc2<SPLIT> (column-group form)
+  LF_FWD_COMBINE,                                    // k_fwd_combine
+  LF_TRI16, LF_TRI8, LF_TRI1,                        // k_panel_tri<16> / <8> / k_panel_tri1
+  LF_ROWS, LF_ROWS_BYC,                              // k_panel_rows / k_panel_rows_byc
+  LF_LEAF4,                                          // k_chol_leaf<4>
+  LF_FACT_1_2, LF_FACT_1_3, LF_FACT_4_3, LF_FACT_8_3, LF_FACT_16_2,   // k_chol_fact<NW, MAXP>
+  LF_FWD1, LF_FWD4, LF_FWD16,                        // k_solve_fwd<NW>
+  LF_FWD_EXT, LF_FWD_TRI,                            // stand-alone forward solve of panel levels
+  LF_BWD_CHAIN, LF_BWD_FUSED, LF_BWD_EXT, LF_BWD_TRI,
+  LF_BWD1, LF_BWD4, LF_BWD8,                         // k_solve_bwd<NW>
+  LF_COUNT
+};
+const char *launch_form_name(int form);
+// what one factor + solve launches: per form, launches and workgroups; per level, rider items carried by its launches and long-list
+// accumulate targets; the backward chain.  A launcher given a census records there and launches nothing.
+struct LaunchCensus {
+  int64_t launches[LF_COUNT] = {}, workgroups[LF_COUNT] = {};
+  // work items: what the form itself works on -- accumulate forms: targets (gather) / groups (column-group), WITHOUT the forward-role
+  // workgroups that ride in the launch and the padding to a multiple of 8; every other form: its workgroups
+  int64_t items[LF_COUNT] = {};
+  std::vector<int> level_riders, level_long;
+  int chain_on = 0, chain_mode = 0;
+  void add(int form, int64_t grid, int64_t n_items = -1) { ++launches[form]; workgroups[form] += grid; items[form] += n_items < 0 ? grid : n_items; }
+};
+LaunchForm select_acc(const HostSchedule &H, int l);       // accumulate launch of level l (gather or column-group form, and its split)
+LaunchForm select_tri(const HostSchedule &H, int l);       // triangle kernel of a panel level
+LaunchForm select_rows(const HostSchedule &H, int l);      // row kernel of a panel level
+LaunchForm select_fact(const HostSchedule &H, int l);      // non-panel level: the leaf kernel or a k_chol_fact width
+LaunchForm select_fwd(const HostSchedule &H, int l);       // non-panel level: k_solve_fwd width
+LaunchForm select_bwd(const HostSchedule &H, int l);       // panel level: LF_BWD_FUSED or LF_BWD_EXT (+ LF_BWD_TRI); else a k_solve_bwd width
 void launch_factor(const DevPlan &P, const HostSchedule &H, const double *Hblk, double *Lv, const double *lambda_p,
                    int *fail_flag, hipStream_t s, const double *b = nullptr, double *x = nullptr, int phase = PHASE_ALL, const PartialSweep *ps = nullptr,
-                   const double *b_full = nullptr);   // (b_full: distributed landmark elimination, see k_dist_rhs)
+                   const double *b_full = nullptr, LaunchCensus *census = nullptr);   // (b_full: distributed landmark elimination, see k_dist_rhs)
 // wildfire back-substitution (kernels.hip k_wild_*): device arrays per task (run, dirty) / per column (chg), the previous solution
 struct Wildfire { unsigned char *run, *chg; const unsigned char *dirty; const double *xprev; double thr; };
 void launch_solve(const DevPlan &P, const HostSchedule &H, const double *Lv, const double *b, double *x, hipStream_t s,
-                  bool fwd_done = false, int phase = PHASE_ALL, const Wildfire *wf = nullptr);
+                  bool fwd_done = false, int phase = PHASE_ALL, const Wildfire *wf = nullptr, LaunchCensus *census = nullptr);
 void launch_mix_rhs(const DevPlan &P, const double *b, const double *ysaved, double *x, const unsigned char *col_dirty, hipStream_t s);
 void launch_copy_vec(const double *src, double *dst, int64_t n, hipStream_t s);
 void launch_mask_poses(const DevPlan &P, const double *poses, double *out, const int *pose_group, int rank, int world, hipStream_t s);

@@ -123,9 +123,12 @@ int fgo_debug_read_reduced(fgo_ctx *c, double lambda, double *H_dense, double *b
   return dense_from_blocks(c, c->ba.d_Hred.p, c->ba.d_bred.p, H_dense, b_dense);
 } FGO_CATCH_INT(c)
 
-int fgo_solve_step(fgo_ctx *c, double lambda, double *delta_out) try {
+// one damped solve, read back in free-variable order.  fused: as an LM trial runs it -- the forward solve riding in the factor sweep
+// (launch_factor with b / x: the accumulate, row and leaf kernels carry the right-hand side, k_fwd_combine joins split rows), then the
+// backward sweep alone; else the stand-alone forward kernels.  One body, so refusals and phantom slots cannot drift apart.
+static int solve_once(fgo_ctx *c, double lambda, double *delta_out, bool fused, const char *who) {
   if (!c || !delta_out) return FGO_EINVAL;
-  if (c->shard_world > 1) return fail(c, FGO_ESTATE, "fgo_solve_step: not available in distributed mode");
+  if (c->shard_world > 1) return fail(c, FGO_ESTATE, (std::string(who) + ": not available in distributed mode").c_str());
   (void)hipSetDevice(c->cfg.device);
   ba_off(c);                                            // delta_out covers every free variable
   int rc = ensure_ready(c);
@@ -134,8 +137,8 @@ int fgo_solve_step(fgo_ctx *c, double lambda, double *delta_out) try {
   hipStream_t s = c->stream;
   claim_L(c);
   HIPCHK(c, stage_lambda(c, lambda));
-  launch_factor(c->plan, c->sched, c->d_H[c->cur].p, c->d_L.p, c->d_scal.p + 3, c->d_fail.p, s);
-  launch_solve(c->plan, c->sched, c->d_L.p, c->d_b[c->cur].p, c->d_x.p, s);
+  launch_factor(c->plan, c->sched, c->d_H[c->cur].p, c->d_L.p, c->d_scal.p + 3, c->d_fail.p, s, fused ? c->d_b[c->cur].p : nullptr, fused ? c->d_x.p : nullptr);
+  launch_solve(c->plan, c->sched, c->d_L.p, c->d_b[c->cur].p, c->d_x.p, s, fused);
   const int nb = c->plan.nb;
   std::vector<double> x((size_t)nb * 6);
   HIPCHK(c, hipMemcpyAsync(x.data(), c->d_x.p, sizeof(double) * x.size(), hipMemcpyDeviceToHost, s));
@@ -146,6 +149,44 @@ int fgo_solve_step(fgo_ctx *c, double lambda, double *delta_out) try {
     if (c->S.perm[k] < nb - c->n_phantom) std::memcpy(delta_out + (size_t)c->S.perm[k] * 6, &x[(size_t)k * 6], 6 * sizeof(double));
   if (*c->h_fail) return fail(c, FGO_ENUM, "block Cholesky: matrix not positive definite");
   return FGO_OK;
+}
+int fgo_solve_step(fgo_ctx *c, double lambda, double *delta_out) try { return solve_once(c, lambda, delta_out, false, "fgo_solve_step"); } FGO_CATCH_INT(c)
+int fgo_debug_solve_fused(fgo_ctx *c, double lambda, double *delta_out) try { return solve_once(c, lambda, delta_out, true, "fgo_debug_solve_fused"); } FGO_CATCH_INT(c)
+
+// tests: which kernel instantiations one factor + solve of the built structure launches (fused != 0: as an LM trial, else as
+// fgo_solve_step).  The launchers themselves are walked with their launches switched off, so the answer cannot drift from them.
+int fgo_debug_launch_census(fgo_ctx *c, int fused, int64_t *launches, int64_t *workgroups, int64_t *items, int form_cap, int *level_riders, int *level_long,
+                            int level_cap, int *chain2, char *names, int names_cap) try {
+  if (!c || form_cap < 0 || level_cap < 0 || names_cap < 0) return FGO_EINVAL;
+  if (c->shard_world > 1) return fail(c, FGO_ESTATE, "fgo_debug_launch_census: not available in distributed mode");
+  (void)hipSetDevice(c->cfg.device);
+  ba_off(c);                                            // the structure fgo_solve_step / fgo_debug_solve_fused run on
+  int rc = ensure_ready(c);
+  if (rc) return rc;
+  LaunchCensus cz;
+  double *const b = c->d_b[c->cur].p, *const x = c->d_x.p;
+  // (launch_factor takes "b / x given" as its sign of the fused form: without the buffers the walk would silently be the stand-alone one)
+  if (!b || !x) return fail(c, FGO_ESTATE, "fgo_debug_launch_census: the right-hand side / solution buffers are not allocated");
+  launch_factor(c->plan, c->sched, c->d_H[c->cur].p, c->d_L.p, c->d_scal.p + 3, c->d_fail.p, c->stream, fused ? b : nullptr, fused ? x : nullptr, PHASE_ALL,
+                nullptr, nullptr, &cz);
+  launch_solve(c->plan, c->sched, c->d_L.p, b, x, c->stream, fused != 0, PHASE_ALL, nullptr, &cz);
+  for (int f = 0; f < std::min<int>(form_cap, LF_COUNT); ++f) {
+    if (launches) launches[f] = cz.launches[f];
+    if (workgroups) workgroups[f] = cz.workgroups[f];
+    if (items) items[f] = cz.items[f];
+  }
+  for (int l = 0; l < std::min(level_cap, c->sched.n_levels); ++l) {
+    if (level_riders) level_riders[l] = cz.level_riders[(size_t)l];
+    if (level_long) level_long[l] = cz.level_long[(size_t)l];
+  }
+  if (chain2) { chain2[0] = cz.chain_on; chain2[1] = cz.chain_mode; }
+  if (names && names_cap > 0) {                         // the forms' names, one per line
+    std::string all;
+    for (int f = 0; f < LF_COUNT; ++f) { all += launch_form_name(f); all += '\n'; }
+    if ((int)all.size() + 1 > names_cap) return fail(c, FGO_EINVAL, "fgo_debug_launch_census: names buffer too small");
+    std::memcpy(names, all.c_str(), all.size() + 1);
+  }
+  return LF_COUNT;
 } FGO_CATCH_INT(c)
 
 int fgo_bench_phase(fgo_ctx *c, int phase, int reps, double *ms_out) try {

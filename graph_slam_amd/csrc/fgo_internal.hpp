@@ -190,7 +190,9 @@ struct Symbolic {
   // column-group accumulate lists (k_chol_acc2): the targets of one column that have external updates, in groups of
   // ACC2_G; per group the external source columns j that touch it, ascending, as (b = block (k, j); a[g] = block (i_g, j)
   // or the zero block).  b is the same for the whole wave (scalar loads), every update reads ONE 288-byte block instead
-  // of two, and the updates of a target still arrive in ascending source order (bit-identical to the gather lists).
+  // of two, and the updates of a target still arrive in ascending source order: bit-identical to the gather lists where both forms
+  // apply a list in one piece (one wave per group / per ten targets, no riders, no long-list role); the split forms cut the
+  // GROUP's list across their waves, the gather form each target's own, so those agree to rounding only (tests/test_gpu_launch_forms.py).
   std::vector<int64_t> g2_lvl;       // nlevels+1 -> groups
   std::vector<int> g2_tgt;           // groups * ACC2_G: target block or -1
   std::vector<int64_t> g2_ptr;       // groups+1 -> entries

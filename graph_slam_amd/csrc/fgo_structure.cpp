@@ -1116,13 +1116,16 @@ struct StructureBuild {
       std::vector<int> order((size_t)S.n_panels);
       for (int pn = 0; pn < S.n_panels; ++pn) order[(size_t)pn] = pn;
       const int mode = (int)tune("tri_lpt", 1);
+      // select_tri reads HostSchedule::cus (set when the context was bound to its device) and level_ptr, nothing else: level_ptr is
+      // filled in here, ahead of the rest of the schedule further down (which assigns the same vector again)
+      c->sched.level_ptr = S.level_ptr;
       if (mode != 0)
         for (size_t l = 0; l + 1 < S.level_ptr.size(); ++l) {
           const int ntf = S.level_ptr[l + 1] - S.level_ptr[l];
           if (!S.level_panel[l] || ntf <= 0) continue;
           const int p0 = S.task_panel[S.level_ptr[l]], p1 = p0 + ntf;
           if (p0 < 0 || p1 > S.n_panels) continue;
-          const bool tri1 = tune("tri1", 1) != 0 && ntf > tri_wide_panels(c->sched.cus) && ntf >= (int)tune("tri1_min", 3 * c->sched.cus);   // (launch_factor's choice)
+          const bool tri1 = select_tri(c->sched, (int)l) == LF_TRI1;   // (launch_factor's choice)
           const bool ascending = mode == 2 || (mode == 1 && tri1);
           if (ascending) std::stable_sort(order.begin() + p0, order.begin() + p1, [&](int a, int b) { return pd[(size_t)a].m < pd[(size_t)b].m; });
           else std::stable_sort(order.begin() + p0, order.begin() + p1, [&](int a, int b) { return pd[(size_t)a].m > pd[(size_t)b].m; });

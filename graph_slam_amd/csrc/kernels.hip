@@ -637,8 +637,10 @@ __global__ __launch_bounds__(SPLIT * 64) void k_chol_acc(DevPlan P, const double
 // loads into SGPRs and costs no vector memory traffic and no LDS exchange -- and lane group g reads only its own A block
 // L(i_g, j) (the zero block where row i_g is not in pattern(j)).  Per update 288 bytes instead of 576 and 3 vector loads
 // instead of 6 + an LDS round trip; the updates of a target arrive in the same ascending source order and with the same
-// arithmetic as in the gather form, so the factor is bit-identical.  SPLIT > 1 splits the entry list across the waves
-// (short dependent chains at the skinny top), partial rows combined from LDS in a fixed order.
+// arithmetic as in the gather form, so with SPLIT == 1 the factor is bit-identical to k_chol_acc<1> applying whole lists (no
+// riders, no long-list role).  SPLIT > 1 splits the GROUP's entry list across the waves (short dependent chains at the skinny
+// top), partial rows combined from LDS in a fixed order: a target's updates then fall to other waves than under the gather
+// form's split of its own list, and the two agree to rounding only.
 template <int SPLIT>
 __global__ __launch_bounds__(SPLIT * 64) void k_chol_acc2(DevPlan P, const double *__restrict__ Hblk, double *__restrict__ Lv,
                                                           const double *__restrict__ Lsrc, int64_t group0, int n_groups,
@@ -2312,11 +2314,92 @@ void launch_update(const DevPlan &P, const double *poses, double *cand, const do
   hipLaunchKernelGGL(k_reduce, dim3(1), dim3(256), 0, s, P.partial, (int64_t)blocks, scalar_out, 0);
 }
 
-static void launch_fwd_level(const DevPlan &P, const HostSchedule &H, const double *Lv, double *x, int l, hipStream_t s) {
+// ---- launch selection (device_plan.hpp): every threshold of the factor / solve launchers, as pure functions of the schedule.
+// The height cuts of the generic kernels choose how many waves share a column or a row, never what a kernel can hold: k_chol_fact
+// takes the blocks beyond MAXP * NW * 10 in overflow passes and the solve kernels stride over a list of any length, so a forced
+// cut-off needs no clamp -- every instantiation is correct (only slower) at every height.
+const char *launch_form_name(int form) {
+  static const char *const names[LF_COUNT] = {
+    "k_chol_acc<8>", "k_chol_acc<4>", "k_chol_acc<2>", "k_chol_acc<1>", "k_chol_acc2<8>", "k_chol_acc2<4>", "k_chol_acc2<1>", "k_fwd_combine",
+    "k_panel_tri<16>", "k_panel_tri<8>", "k_panel_tri1", "k_panel_rows", "k_panel_rows_byc", "k_chol_leaf<4>",
+    "k_chol_fact<1,2>", "k_chol_fact<1,3>", "k_chol_fact<4,3>", "k_chol_fact<8,3>", "k_chol_fact<16,2>",
+    "k_solve_fwd<1>", "k_solve_fwd<4>", "k_solve_fwd<16>", "k_fwd_ext", "k_fwd_tri",
+    "k_bwd_chain", "k_bwd_fused", "k_bwd_ext", "k_bwd_tri", "k_solve_bwd<1>", "k_solve_bwd<4>", "k_solve_bwd<8>"};
+  return form >= 0 && form < LF_COUNT ? names[form] : "?";
+}
+LaunchForm select_acc(const HostSchedule &H, int l) {
+  const int n_g2_full = H.g2_lvl.empty() ? 0 : (int)(H.g2_lvl[l + 1] - H.g2_lvl[l]);
+  if (n_g2_full > 0) {      // (the symbolic phase builds these lists for the very wide levels only: FGO_ACC2_MIN)
+    // column-group form (scalar B operand).  Split the entry lists where there are few groups (short chains at the top)
+    static const int g2_narrow = (int)tune("acc2_narrow", 400);
+    static const int g2_mid = (int)tune("acc2_mid", 6000);
+    return n_g2_full <= g2_narrow ? LF_ACC2_8 : n_g2_full <= g2_mid ? LF_ACC2_4 : LF_ACC2_1;   // (by the level's FULL list, partial sweep or not)
+  }
+  const int64_t n = H.acc_ptr[l + 1] - H.acc_ptr[l];
+  // few targets (the skinny top of the tree): split every source list 8 ways to shorten the dependent chain
+  static const int64_t narrow_max = (int64_t)tune("acc_narrow", 4000);
+  // very many targets (the lowest panel levels: short lists, 10^5 .. 10^6 targets): one wave per 10 targets, no
+  // split-K and no LDS combine -- the launch is bound by how many independent waves are in flight, not by the
+  // length of a list (cfg 2: factor sweep 5.98 -> 5.73 ms, cfg 5: 35.9 -> 33.0 ms)
+  static const int64_t acc_wide2 = (int64_t)tune("acc_wide2", 60000);
+  static const int64_t acc_mid2 = (int64_t)tune("acc_mid2", 15000);   // in between: split two ways (3.78 -> 3.74 ms)
+  static const int acc_wide_split = (int)tune("acc_wide_split", 1);
+  if (n <= narrow_max) return LF_ACC8;
+  if (n > acc_wide2) return acc_wide_split == 1 ? LF_ACC1 : LF_ACC2;
+  return n > acc_mid2 ? LF_ACC2 : LF_ACC4;
+}
+LaunchForm select_tri(const HostSchedule &H, int l) {
+  const int ntf = H.level_ptr[l + 1] - H.level_ptr[l];         // the whole level (kernel choices go by it)
+  // 16 waves hold a panel's trailing matrix with the fewest tiles per wave, but their registers allow one workgroup
+  // per CU; levels with more panels than CUs run the 8-wave instantiation, two workgroups per CU
+  const int tri_wide = tri_wide_panels(H.cus);
+  // (a 4-wave instantiation with four workgroups per CU for the very wide levels -- twice the pivot chains in flight --
+  //  was measured slower: cfg 2 factor sweep 3.27 -> 3.34 ms, cfg 5 21.5 -> 22.3 ms)
+  // wide levels: the throughput form, one wave per panel (FGO_TRI1=0: the 8-wave latency form, two workgroups per CU)
+  static const int tri1_on = (int)tune("tri1", 1);
+  // (one wave per panel holds 4 panels per CU: it beats two 8-wave workgroups per CU once there are >= 3 rounds of those)
+  const int tri1_min = (int)tune("tri1_min", 3 * H.cus);
+  if (tri1_on && ntf > tri_wide && ntf >= tri1_min) return LF_TRI1;
+  return ntf > tri_wide ? LF_TRI8 : LF_TRI16;
+}
+LaunchForm select_rows(const HostSchedule &H, int l) { return l >= H.rows_byc_level ? LF_ROWS_BYC : LF_ROWS; }
+LaunchForm select_fact(const HostSchedule &H, int l) {
+  if (!H.level_leaf.empty() && H.level_leaf[l]) return LF_LEAF4;
+  // single-column tasks (the landmarks of a bundle adjustment): one wave per task instead of four; columns of <= 20
+  // blocks keep two register passes instead of three (fewer VGPRs, more waves per SIMD)
+  static const int h1_2 = (int)tune("fact_h1_2", 20), h1_3 = (int)tune("fact_h1_3", 30), h4 = (int)tune("fact_h4", 120), h8 = (int)tune("fact_h8", 240);
+  const bool single = H.level_maxtaskcols[l] == 1;
+  const int h = H.level_maxcol[l];
+  if (single && h <= h1_2) return LF_FACT_1_2;
+  if (single && h <= h1_3) return LF_FACT_1_3;
+  return h <= h4 ? LF_FACT_4_3 : h <= h8 ? LF_FACT_8_3 : LF_FACT_16_2;
+}
+LaunchForm select_fwd(const HostSchedule &H, int l) {
+  static const int h1 = (int)tune("fwd_h1", 40), h4 = (int)tune("fwd_h4", 160);
+  if (H.level_maxtaskcols[l] == 1 && H.level_maxrow[l] <= h1) return LF_FWD1;
+  return H.level_maxrow[l] <= h4 ? LF_FWD4 : LF_FWD16;
+}
+LaunchForm select_bwd(const HostSchedule &H, int l) {
+  if (H.level_panel[l]) {
+    // few panels (the top of the tree): one fused launch per level, a 16-wave workgroup per panel
+    static const int bwd_fused_max = (int)tune("bwd_fused", 256);   // swept 0 / 32 / 128 / 256 / 512 / 4096 on cfg 2: 137.3 / 138.4 / 138.9 / 139.0 / 139.0 / 132.6 it/s
+    return H.level_ptr[l + 1] - H.level_ptr[l] <= bwd_fused_max ? LF_BWD_FUSED : LF_BWD_EXT;
+  }
+  static const int h1 = (int)tune("bwd_h1", 20), h4 = (int)tune("bwd_h4", 80);
+  if (H.level_maxtaskcols[l] == 1 && H.level_maxcol[l] <= h1) return LF_BWD1;
+  return H.level_maxcol[l] <= h4 ? LF_BWD4 : LF_BWD8;
+}
+// a launch, or (census) its record: the launchers below are walked unchanged by fgo_debug_launch_census
+#define FGO_LAUNCH(cz, form, grid, ...) do { if (cz) (cz)->add((form), (int64_t)(grid)); else hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+#define FGO_LAUNCH_N(cz, form, grid, items, ...) do { if (cz) (cz)->add((form), (int64_t)(grid), (int64_t)(items)); else hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+
+static void launch_fwd_level(const DevPlan &P, const HostSchedule &H, const double *Lv, double *x, int l, hipStream_t s, LaunchCensus *cz) {
   const int t0 = H.level_ptr[l], nt = H.level_ptr[l + 1] - t0;
-  if (H.level_maxtaskcols[l] == 1 && H.level_maxrow[l] <= 40) hipLaunchKernelGGL(k_solve_fwd<1>, dim3(nt), dim3(64), 0, s, P, Lv, x, t0);
-  else if (H.level_maxrow[l] <= 160) hipLaunchKernelGGL(k_solve_fwd<4>, dim3(nt), dim3(256), 0, s, P, Lv, x, t0);
-  else hipLaunchKernelGGL(k_solve_fwd<16>, dim3(nt), dim3(1024), 0, s, P, Lv, x, t0);
+  switch (select_fwd(H, l)) {
+    case LF_FWD1: FGO_LAUNCH(cz, LF_FWD1, nt, k_solve_fwd<1>, dim3(nt), dim3(64), 0, s, P, Lv, x, t0); break;
+    case LF_FWD4: FGO_LAUNCH(cz, LF_FWD4, nt, k_solve_fwd<4>, dim3(nt), dim3(256), 0, s, P, Lv, x, t0); break;
+    default: FGO_LAUNCH(cz, LF_FWD16, nt, k_solve_fwd<16>, dim3(nt), dim3(1024), 0, s, P, Lv, x, t0); break;
+  }
 }
 void launch_copy_vec(const double *src, double *dst, int64_t n, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_copy, dim3((unsigned)std::min<int64_t>(1024, (n + 255) / 256)), dim3(256), 0, s, src, dst, n);
@@ -2356,9 +2439,10 @@ void launch_mask_poses(const DevPlan &P, const double *poses, double *out, const
 }
 
 void launch_factor(const DevPlan &P, const HostSchedule &H, const double *Hblk, double *Lv, const double *lambda_p,
-                   int *fail_flag, hipStream_t s, const double *b, double *x, int phase, const PartialSweep *ps, const double *b_full) {
+                   int *fail_flag, hipStream_t s, const double *b, double *x, int phase, const PartialSweep *ps, const double *b_full, LaunchCensus *cz) {
   // (partial sweep, P.task_dirty set: the caller has prepared x = b on the dirty columns and the saved y elsewhere)
-  if (x && phase != PHASE_TOP && !P.task_dirty) launch_copy(b, x, (int64_t)P.top_col0 * 6, s);   // (the top of x is written by k_dist_rhs when distributed)
+  if (x && phase != PHASE_TOP && !P.task_dirty && !cz) launch_copy(b, x, (int64_t)P.top_col0 * 6, s);   // (the top of x is written by k_dist_rhs when distributed)
+  if (cz) { cz->level_riders.assign((size_t)H.n_levels, 0); cz->level_long.assign((size_t)H.n_levels, 0); }
   for (int l = 0; l < H.n_levels; ++l) {
     if (!seg_runs(H, l, phase)) continue;
     const int64_t a0 = H.acc_ptr[l], am = H.acc_mid[l], a1 = H.acc_ptr[l + 1];
@@ -2381,91 +2465,71 @@ void launch_factor(const DevPlan &P, const HostSchedule &H, const double *Hblk, 
     const int n_g2_full = H.g2_lvl.empty() ? 0 : (int)(H.g2_lvl[l + 1] - H.g2_lvl[l]);
     const int64_t g2f = (!ps || n_g2_full == 0) ? (H.g2_lvl.empty() ? 0 : H.g2_lvl[l]) : (nothing_dirty ? H.g2_lvl[l] : ps->g0[ta]);
     const int n_g2 = (!ps || n_g2_full == 0) ? n_g2_full : (nothing_dirty ? 0 : ps->g1[tb] - ps->g0[ta]);
-    if (n_g2_full > 0) {      // (the symbolic phase builds these lists for the very wide levels only: FGO_ACC2_MIN)
-      // column-group form (scalar B operand).  Split the entry lists where there are few groups (short chains at the top)
-      static const int g2_narrow = (int)tune("acc2_narrow", 400);
-      static const int g2_mid = (int)tune("acc2_mid", 6000);
-      const int grid2 = n_g2 + n_fwd_wg;                      // (which instantiation: by the level's FULL list, partial sweep or not)
-      if (grid2 <= 0) {}
-      else if (n_g2_full <= g2_narrow) hipLaunchKernelGGL(k_chol_acc2<8>, dim3(grid2), dim3(512), 0, s, P, Hblk, Lv, Lv, g2f, n_g2, lambda_p, x, col0);
-      else if (n_g2_full <= g2_mid) hipLaunchKernelGGL(k_chol_acc2<4>, dim3(grid2), dim3(256), 0, s, P, Hblk, Lv, Lv, g2f, n_g2, lambda_p, x, col0);
-      else hipLaunchKernelGGL(k_chol_acc2<1>, dim3(grid2), dim3(64), 0, s, P, Hblk, Lv, Lv, g2f, n_g2, lambda_p, x, col0);
-    } else if (grid > 0) {
-      // few targets (the skinny top of the tree): split every source list 8 ways to shorten the dependent chain
-      static const int64_t narrow_max = (int64_t)tune("acc_narrow", 4000);
-      // very many targets (the lowest panel levels: short lists, 10^5 .. 10^6 targets): one wave per 10 targets, no
-      // split-K and no LDS combine -- the launch is bound by how many independent waves are in flight, not by the
-      // length of a list (cfg 2: factor sweep 5.98 -> 5.73 ms, cfg 5: 35.9 -> 33.0 ms)
-      static const int64_t acc_wide2 = (int64_t)tune("acc_wide2", 60000);
-      static const int64_t acc_mid2 = (int64_t)tune("acc_mid2", 15000);   // in between: split two ways (3.78 -> 3.74 ms)
-      static const int acc_wide_split = (int)tune("acc_wide_split", 1);
-      if (a1 - a0 <= narrow_max)
-        hipLaunchKernelGGL(k_chol_acc<8>, dim3(grid), dim3(512), 0, s, P, Hblk, Lv, sf, sn, lambda_p, x, n_acc_wg, col0, n_long, lf);
-      else if (a1 - a0 > acc_wide2) {
-        if (acc_wide_split == 1) hipLaunchKernelGGL(k_chol_acc<1>, dim3(grid), dim3(64), 0, s, P, Hblk, Lv, sf, sn, lambda_p, x, n_acc_wg, col0, n_long, lf);
-        else hipLaunchKernelGGL(k_chol_acc<2>, dim3(grid), dim3(128), 0, s, P, Hblk, Lv, sf, sn, lambda_p, x, n_acc_wg, col0, n_long, lf);
-      } else if (a1 - a0 > acc_mid2)
-        hipLaunchKernelGGL(k_chol_acc<2>, dim3(grid), dim3(128), 0, s, P, Hblk, Lv, sf, sn, lambda_p, x, n_acc_wg, col0, n_long, lf);
-      else
-        hipLaunchKernelGGL(k_chol_acc<4>, dim3(grid), dim3(256), 0, s, P, Hblk, Lv, sf, sn, lambda_p, x, n_acc_wg, col0, n_long, lf);
-    }
+    const int grid2 = n_g2 + n_fwd_wg;
+    const LaunchForm acc = select_acc(H, l);
+    const bool acc_g2 = acc == LF_ACC2_8 || acc == LF_ACC2_4 || acc == LF_ACC2_1;
+    if (cz && !acc_g2 && grid > 0) cz->level_long[(size_t)l] = n_long;
+    if (acc_g2 ? grid2 > 0 : grid > 0)
+      switch (acc) {
+        case LF_ACC2_8: FGO_LAUNCH_N(cz, acc, grid2, n_g2, k_chol_acc2<8>, dim3(grid2), dim3(512), 0, s, P, Hblk, Lv, Lv, g2f, n_g2, lambda_p, x, col0); break;
+        case LF_ACC2_4: FGO_LAUNCH_N(cz, acc, grid2, n_g2, k_chol_acc2<4>, dim3(grid2), dim3(256), 0, s, P, Hblk, Lv, Lv, g2f, n_g2, lambda_p, x, col0); break;
+        case LF_ACC2_1: FGO_LAUNCH_N(cz, acc, grid2, n_g2, k_chol_acc2<1>, dim3(grid2), dim3(64), 0, s, P, Hblk, Lv, Lv, g2f, n_g2, lambda_p, x, col0); break;
+        case LF_ACC8: FGO_LAUNCH_N(cz, acc, grid, sn + n_long, k_chol_acc<8>, dim3(grid), dim3(512), 0, s, P, Hblk, Lv, sf, sn, lambda_p, x, n_acc_wg, col0, n_long, lf); break;
+        case LF_ACC4: FGO_LAUNCH_N(cz, acc, grid, sn + n_long, k_chol_acc<4>, dim3(grid), dim3(256), 0, s, P, Hblk, Lv, sf, sn, lambda_p, x, n_acc_wg, col0, n_long, lf); break;
+        case LF_ACC2: FGO_LAUNCH_N(cz, acc, grid, sn + n_long, k_chol_acc<2>, dim3(grid), dim3(128), 0, s, P, Hblk, Lv, sf, sn, lambda_p, x, n_acc_wg, col0, n_long, lf); break;
+        default: FGO_LAUNCH_N(cz, LF_ACC1, grid, sn + n_long, k_chol_acc<1>, dim3(grid), dim3(64), 0, s, P, Hblk, Lv, sf, sn, lambda_p, x, n_acc_wg, col0, n_long, lf); break;
+      }
     if (x && H.level_panel[l] && !H.fsplit_ptr.empty() && H.fsplit_ptr[l + 1] > H.fsplit_ptr[l] && !nothing_dirty)
-      hipLaunchKernelGGL(k_fwd_combine, dim3(H.fsplit_ptr[l + 1] - H.fsplit_ptr[l]), dim3(64), 0, s, P, x, H.fsplit_ptr[l]);
+      FGO_LAUNCH(cz, LF_FWD_COMBINE, H.fsplit_ptr[l + 1] - H.fsplit_ptr[l], k_fwd_combine, dim3(H.fsplit_ptr[l + 1] - H.fsplit_ptr[l]), dim3(64), 0, s, P, x, H.fsplit_ptr[l]);
     const int t0f = H.level_ptr[l], ntf = H.level_ptr[l + 1] - t0f;          // the whole level (kernel choices go by it)
     const int t0 = ps ? (nothing_dirty ? t0f : ta) : t0f, nt = ps ? (nothing_dirty ? 0 : tb - ta + 1) : ntf;
     const int pn0 = H.level_panel[l] ? H.level_pn0[l] + (t0 - t0f) : 0;     // (the panels of a level are numbered in task order)
     if (H.level_panel[l]) {
-      // 16 waves hold a panel's trailing matrix with the fewest tiles per wave, but their registers allow one workgroup
-      // per CU; levels with more panels than CUs run the 8-wave instantiation, two workgroups per CU
-      const int tri_wide = tri_wide_panels(H.cus);
-      // (a 4-wave instantiation with four workgroups per CU for the very wide levels -- twice the pivot chains in flight --
-      //  was measured slower: cfg 2 factor sweep 3.27 -> 3.34 ms, cfg 5 21.5 -> 22.3 ms)
-      // wide levels: the throughput form, one wave per panel (FGO_TRI1=0: the 8-wave latency form, two workgroups per CU)
-      static const int tri1_on = (int)tune("tri1", 1);
-      // (one wave per panel holds 4 panels per CU: it beats two 8-wave workgroups per CU once there are >= 3 rounds of those)
-      const int tri1_min = (int)tune("tri1_min", 3 * H.cus);
-      const bool tri1 = tri1_on && ntf > tri_wide && ntf >= tri1_min;
-      if (tri1) {
-        if (nt > 0) hipLaunchKernelGGL(k_panel_tri1, dim3(nt), dim3(64), 0, s, P, Hblk, Lv, pn0, lambda_p, fail_flag);
-      } else if (ntf > tri_wide) {
-        if (nt > 0) hipLaunchKernelGGL((k_panel_tri<8>), dim3(nt), dim3(8 * 64), 0, s, P, Hblk, Lv, pn0, lambda_p, fail_flag, nt, 0, 0, nt);
-      } else {
-        const int r0 = H.ride_ptr.empty() ? 0 : H.ride_ptr[2 * l], nr = H.ride_ptr.empty() ? 0 : H.ride_ptr[2 * l + 1] - r0;
-        const int ntp = (nr > 0 && P.ride_xcd) ? (nt + 7) & ~7 : nt;      // riders start at a multiple of 8: XCD = (blockIdx - ntp) & 7
-        if (ntp + nr > 0)
-          hipLaunchKernelGGL((k_panel_tri<TRI_NW>), dim3(ntp + (nr + RIDE_PER_WG - 1) / RIDE_PER_WG), dim3(TRI_NW * 64), 0, s, P, Hblk, Lv, pn0, lambda_p, fail_flag, ntp, r0, nr, nt);
+      switch (select_tri(H, l)) {
+        case LF_TRI1:
+          if (nt > 0) FGO_LAUNCH(cz, LF_TRI1, nt, k_panel_tri1, dim3(nt), dim3(64), 0, s, P, Hblk, Lv, pn0, lambda_p, fail_flag);
+          break;
+        case LF_TRI8:
+          if (nt > 0) FGO_LAUNCH(cz, LF_TRI8, nt, (k_panel_tri<8>), dim3(nt), dim3(8 * 64), 0, s, P, Hblk, Lv, pn0, lambda_p, fail_flag, nt, 0, 0, nt);
+          break;
+        default: {
+          const int r0 = H.ride_ptr.empty() ? 0 : H.ride_ptr[2 * l], nr = H.ride_ptr.empty() ? 0 : H.ride_ptr[2 * l + 1] - r0;
+          const int ntp = (nr > 0 && P.ride_xcd) ? (nt + 7) & ~7 : nt;      // riders start at a multiple of 8: XCD = (blockIdx - ntp) & 7
+          if (ntp + nr > 0) {
+            if (cz) cz->level_riders[(size_t)l] += nr;
+            FGO_LAUNCH(cz, LF_TRI16, ntp + (nr + RIDE_PER_WG - 1) / RIDE_PER_WG, (k_panel_tri<TRI_NW>), dim3(ntp + (nr + RIDE_PER_WG - 1) / RIDE_PER_WG), dim3(TRI_NW * 64), 0, s, P, Hblk, Lv, pn0, lambda_p, fail_flag, ntp, r0, nr, nt);
+          }
+        }
       }
       const int c0 = !ps ? H.rchunk_ptr[l] : (nothing_dirty ? H.rchunk_ptr[l] : ps->c0[ta]);
       const int nc = !ps ? H.rchunk_ptr[l + 1] - H.rchunk_ptr[l] : (nothing_dirty ? 0 : ps->c1[tb] - ps->c0[ta]);
       const int q0 = H.ride_ptr.empty() ? 0 : H.ride_ptr[2 * l + 1], nq = H.ride_ptr.empty() ? 0 : H.ride_ptr[2 * l + 2] - q0;   // riders of the row launch
       if (nc + nq > 0) {
-        if (l >= H.rows_byc_level) hipLaunchKernelGGL(k_panel_rows_byc, dim3(nc + nq), dim3(64), 0, s, P, Hblk, Lv, c0, x, nc, lambda_p, q0);
-        else hipLaunchKernelGGL(k_panel_rows, dim3(nc + nq), dim3(64), 0, s, P, Hblk, Lv, c0, x, nc, lambda_p, q0);
+        if (cz) cz->level_riders[(size_t)l] += nq;
+        if (select_rows(H, l) == LF_ROWS_BYC) FGO_LAUNCH(cz, LF_ROWS_BYC, nc + nq, k_panel_rows_byc, dim3(nc + nq), dim3(64), 0, s, P, Hblk, Lv, c0, x, nc, lambda_p, q0);
+        else FGO_LAUNCH(cz, LF_ROWS, nc + nq, k_panel_rows, dim3(nc + nq), dim3(64), 0, s, P, Hblk, Lv, c0, x, nc, lambda_p, q0);
       }
       continue;
     }
     if (nt <= 0) continue;                              // (partial sweep: nothing dirty in this level)
-    if (!H.level_leaf.empty() && H.level_leaf[l]) {
-      const int lb = H.level_leaf_maxblk[l], lc = H.level_maxtaskcols[l];
-      const size_t lds = ((size_t)lb + 1) * 36 * sizeof(double) + (size_t)12 * lc * sizeof(double) + ((size_t)lb + 2 + lc + 2) * sizeof(int) +
-                         ((size_t)lb + 2) * sizeof(unsigned short) + (size_t)H.level_leaf_maxops[l] * sizeof(unsigned);
-      hipLaunchKernelGGL((k_chol_leaf<4>), dim3(nt), dim3(256), lds, s, P, Hblk, Lv, t0, lambda_p, fail_flag, lb, lc, x);
-      continue;                                         // (the forward solve of a leaf level is part of the kernel)
-    } else if (H.level_maxtaskcols[l] == 1 && H.level_maxcol[l] <= 20)
-      // single-column tasks (the landmarks of a bundle adjustment): one wave per task instead of four; columns of <= 20
-      // blocks keep two register passes instead of three (fewer VGPRs, more waves per SIMD)
-      hipLaunchKernelGGL((k_chol_fact<1, 2>), dim3(nt), dim3(64), 0, s, P, Hblk, Lv, t0, lambda_p, fail_flag);
-    else if (H.level_maxtaskcols[l] == 1 && H.level_maxcol[l] <= 30)
-      hipLaunchKernelGGL((k_chol_fact<1, 3>), dim3(nt), dim3(64), 0, s, P, Hblk, Lv, t0, lambda_p, fail_flag);
-    else if (H.level_maxcol[l] <= 120)
-      hipLaunchKernelGGL((k_chol_fact<4, 3>), dim3(nt), dim3(256), 0, s, P, Hblk, Lv, t0, lambda_p, fail_flag);
-    else if (H.level_maxcol[l] <= 240)
-      hipLaunchKernelGGL((k_chol_fact<8, 3>), dim3(nt), dim3(512), 0, s, P, Hblk, Lv, t0, lambda_p, fail_flag);
-    else
-      hipLaunchKernelGGL((k_chol_fact<16, 2>), dim3(nt), dim3(1024), 0, s, P, Hblk, Lv, t0, lambda_p, fail_flag);
-    if (x) launch_fwd_level(P, H, Lv, x, l, s);
+    const LaunchForm fact = select_fact(H, l);
+    switch (fact) {
+      case LF_LEAF4: {
+        const int lb = H.level_leaf_maxblk[l], lc = H.level_maxtaskcols[l];
+        const size_t lds = ((size_t)lb + 1) * 36 * sizeof(double) + (size_t)12 * lc * sizeof(double) + ((size_t)lb + 2 + lc + 2) * sizeof(int) +
+                           ((size_t)lb + 2) * sizeof(unsigned short) + (size_t)H.level_leaf_maxops[l] * sizeof(unsigned);
+        FGO_LAUNCH(cz, LF_LEAF4, nt, (k_chol_leaf<4>), dim3(nt), dim3(256), lds, s, P, Hblk, Lv, t0, lambda_p, fail_flag, lb, lc, x);
+        break;                                          // (the forward solve of a leaf level is part of the kernel)
+      }
+      case LF_FACT_1_2: FGO_LAUNCH(cz, fact, nt, (k_chol_fact<1, 2>), dim3(nt), dim3(64), 0, s, P, Hblk, Lv, t0, lambda_p, fail_flag); break;
+      case LF_FACT_1_3: FGO_LAUNCH(cz, fact, nt, (k_chol_fact<1, 3>), dim3(nt), dim3(64), 0, s, P, Hblk, Lv, t0, lambda_p, fail_flag); break;
+      case LF_FACT_4_3: FGO_LAUNCH(cz, fact, nt, (k_chol_fact<4, 3>), dim3(nt), dim3(256), 0, s, P, Hblk, Lv, t0, lambda_p, fail_flag); break;
+      case LF_FACT_8_3: FGO_LAUNCH(cz, fact, nt, (k_chol_fact<8, 3>), dim3(nt), dim3(512), 0, s, P, Hblk, Lv, t0, lambda_p, fail_flag); break;
+      default: FGO_LAUNCH(cz, LF_FACT_16_2, nt, (k_chol_fact<16, 2>), dim3(nt), dim3(1024), 0, s, P, Hblk, Lv, t0, lambda_p, fail_flag); break;
+    }
+    if (x && fact != LF_LEAF4) launch_fwd_level(P, H, Lv, x, l, s, cz);
   }
-  if (phase == PHASE_DOMAIN) {
+  if (phase == PHASE_DOMAIN && !cz) {
     // this rank's contributions to the top: every block of the top columns, and (forward solve fused) their right-hand side
     if (H.n_top_blocks > 0) hipLaunchKernelGGL(k_dist_acc, dim3(cdiv(H.n_top_blocks, 10)), dim3(64), 0, s, P, Hblk, Lv, lambda_p);
     if (x && H.n_top_cols > 0) hipLaunchKernelGGL(k_dist_rhs, dim3(H.n_top_cols), dim3(64), 0, s, P, Lv, b, x, b_full);
@@ -2518,19 +2582,19 @@ __global__ __launch_bounds__(64) void k_wild_mark(DevPlan P, double *__restrict_
 
 // fwd_done: x already holds y (forward solve fused into launch_factor); only the backward sweep runs
 void launch_solve(const DevPlan &P, const HostSchedule &H, const double *Lv, const double *b, double *x, hipStream_t s, bool fwd_done, int phase,
-                  const Wildfire *wf) {
+                  const Wildfire *wf, LaunchCensus *cz) {
   if (!fwd_done) {                                            // stand-alone forward solve: single-GPU entry points only
-    launch_copy(b, x, (int64_t)P.nb * 6, s);
+    if (!cz) launch_copy(b, x, (int64_t)P.nb * 6, s);
     for (int l = 0; l < H.n_levels; ++l) {
       if (!seg_runs(H, l, PHASE_ALL)) continue;
       const int t0 = H.level_ptr[l], nt = H.level_ptr[l + 1] - t0;
       if (H.level_panel[l]) {
         const int c0 = H.fchunk_ptr[l], nc = H.fchunk_ptr[l + 1] - c0;
-        if (nc > 0) hipLaunchKernelGGL(k_fwd_ext, dim3(nc), dim3(256), 0, s, P, Lv, x, c0);
-        hipLaunchKernelGGL(k_fwd_tri, dim3(nt), dim3(64), 0, s, P, x, H.level_pn0[l]);
+        if (nc > 0) FGO_LAUNCH(cz, LF_FWD_EXT, nc, k_fwd_ext, dim3(nc), dim3(256), 0, s, P, Lv, x, c0);
+        FGO_LAUNCH(cz, LF_FWD_TRI, nt, k_fwd_tri, dim3(nt), dim3(64), 0, s, P, x, H.level_pn0[l]);
         continue;
       }
-      launch_fwd_level(P, H, Lv, x, l, s);
+      launch_fwd_level(P, H, Lv, x, l, s, cz);
     }
   }
   // backward sweep.  Distributed: the top first (replicated on every rank), then this rank's own domain -- a domain
@@ -2538,13 +2602,14 @@ void launch_solve(const DevPlan &P, const HostSchedule &H, const double *Lv, con
   // (distributed: the chain is the replicated top's, part of the PHASE_TOP pass)
   const bool chain = (phase == PHASE_ALL || phase == PHASE_TOP) && H.bchain_low >= 0 && H.bchain_n > 0;
   static const int chain_mode = (int)tune("bwd_chain_mode", 5);   // 1: agent-scope loads of x instead of an acquire fence (no L2 invalidation), 2: agent-scope stores + store-acknowledge wait instead of the release fence, 4: operands touched before the wait.  cfg 2 backward sweep: no chain 0.799, modes 0 / 1 / 3 / 7: 0.815 / 0.747 / 0.737 / 0.735 ms
+  if (cz) { cz->chain_on = chain ? 1 : 0; cz->chain_mode = chain_mode; }
   if (chain) {
     // the progress counter starts every launch at zero whatever happened to the launch before (an aborted launch would leave
     // it armed and let every later wait pass early): a 4-byte kernel node in front, part of the captured trial
-    hipLaunchKernelGGL(k_zero_int, dim3(1), dim3(1), 0, s, reinterpret_cast<int *>(P.pp.bchain_done));
-    hipLaunchKernelGGL(k_bwd_chain, dim3(H.bchain_n), dim3(BWD_NW * 64), 0, s, P, Lv, x, H.bchain_n, chain_mode);      // (items: root level first)
+    if (!cz) hipLaunchKernelGGL(k_zero_int, dim3(1), dim3(1), 0, s, reinterpret_cast<int *>(P.pp.bchain_done));
+    FGO_LAUNCH(cz, LF_BWD_CHAIN, H.bchain_n, k_bwd_chain, dim3(H.bchain_n), dim3(BWD_NW * 64), 0, s, P, Lv, x, H.bchain_n, chain_mode);      // (items: root level first)
   }
-  const bool wild = wf && chain && phase == PHASE_ALL;       // (the chain's levels are always solved: they are the dirty root paths)
+  const bool wild = wf && chain && phase == PHASE_ALL && !cz;       // (the chain's levels are always solved: they are the dirty root paths)
   DevPlan Pw = P;
   if (wild) {
     Pw.task_dirty = wf->run;
@@ -2559,22 +2624,18 @@ void launch_solve(const DevPlan &P, const HostSchedule &H, const double *Lv, con
     // wildfire: which tasks of the level are solved again -- before its kernels; afterwards which of its columns moved
     auto level_done = [&]() { if (wild) hipLaunchKernelGGL(k_wild_mark, dim3(nt), dim3(64), 0, s, P, x, wf->xprev, wf->run, wf->chg, wf->thr, t0, (const ChainItem *)nullptr); };
     if (wild) hipLaunchKernelGGL(k_wild_decide, dim3(nt), dim3(64), 0, s, P, wf->dirty, wf->chg, wf->run, t0, H.level_panel[l] ? 1 : 0);
-    if (H.level_panel[l]) {
-      // few panels (the top of the tree): one fused launch per level, a 16-wave workgroup per panel
-      static const int bwd_fused_max = (int)tune("bwd_fused", 256);   // swept 0 / 32 / 128 / 256 / 512 / 4096 on cfg 2: 137.3 / 138.4 / 138.9 / 139.0 / 139.0 / 132.6 it/s
-      if (nt <= bwd_fused_max) {
-        hipLaunchKernelGGL(k_bwd_fused, dim3(nt), dim3(BWD_NW * 64), 0, s, PL, Lv, x, H.level_pn0[l]);
-        level_done(); continue;
+    switch (select_bwd(H, l)) {
+      case LF_BWD_FUSED: FGO_LAUNCH(cz, LF_BWD_FUSED, nt, k_bwd_fused, dim3(nt), dim3(BWD_NW * 64), 0, s, PL, Lv, x, H.level_pn0[l]); break;
+      case LF_BWD_EXT: {
+        const int c0 = H.pchunk_ptr[l], nc = H.pchunk_ptr[l + 1] - c0;
+        if (nc > 0) FGO_LAUNCH(cz, LF_BWD_EXT, nc, k_bwd_ext, dim3(nc), dim3(64), 0, s, PL, Lv, x, c0);
+        FGO_LAUNCH(cz, LF_BWD_TRI, nt, k_bwd_tri, dim3(nt), dim3(64), 0, s, PL, x, H.level_pn0[l]);
+        break;
       }
-      const int c0 = H.pchunk_ptr[l], nc = H.pchunk_ptr[l + 1] - c0;
-      if (nc > 0) hipLaunchKernelGGL(k_bwd_ext, dim3(nc), dim3(64), 0, s, PL, Lv, x, c0);
-      hipLaunchKernelGGL(k_bwd_tri, dim3(nt), dim3(64), 0, s, PL, x, H.level_pn0[l]);
-      level_done();
-      continue;
+      case LF_BWD1: FGO_LAUNCH(cz, LF_BWD1, nt, k_solve_bwd<1>, dim3(nt), dim3(64), 0, s, PL, Lv, x, t0); break;
+      case LF_BWD4: FGO_LAUNCH(cz, LF_BWD4, nt, k_solve_bwd<4>, dim3(nt), dim3(256), 0, s, PL, Lv, x, t0); break;
+      default: FGO_LAUNCH(cz, LF_BWD8, nt, k_solve_bwd<8>, dim3(nt), dim3(512), 0, s, PL, Lv, x, t0); break;
     }
-    if (H.level_maxtaskcols[l] == 1 && H.level_maxcol[l] <= 20) hipLaunchKernelGGL(k_solve_bwd<1>, dim3(nt), dim3(64), 0, s, PL, Lv, x, t0);
-    else if (H.level_maxcol[l] <= 80) hipLaunchKernelGGL(k_solve_bwd<4>, dim3(nt), dim3(256), 0, s, PL, Lv, x, t0);
-    else hipLaunchKernelGGL(k_solve_bwd<8>, dim3(nt), dim3(512), 0, s, PL, Lv, x, t0);
     level_done();
   }
 }

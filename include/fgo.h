@@ -678,6 +678,20 @@ int fgo_debug_read_system(fgo_ctx *ctx, double *H, double *b, double *chi2);
  * g = b_c - W (H_pp + lambda I)^-1 b_p at the current estimate, dense row-major (6 n)^2 / 6 n with n = *n_out = the free
  * non-landmark variables in the order they were added (n <= 4096).  FGO_ESTATE if no landmarks are eliminated. */
 int fgo_debug_read_reduced(fgo_ctx *ctx, double lambda, double *H_dense, double *b_dense, int64_t *n_out);
+/* tests: one damped solve (H + lambda I) d = b as an LM trial runs it -- the forward solve fused into the factor sweep, then the
+ * backward sweep alone -- where fgo_solve_step runs the stand-alone forward kernels.  d in the order of fgo_solve_step, same
+ * refusals (FGO_ESTATE in distributed mode; phantom slots of the incremental mode are not reported). */
+int fgo_debug_solve_fused(fgo_ctx *ctx, double lambda, double *delta_out);
+/* tests: which kernel instantiations one factor + solve of the built structure launches, without launching anything (the launchers
+ * are walked with their launches switched off).  fused != 0: as fgo_debug_solve_fused / an LM trial, 0: as fgo_solve_step.
+ * launches / workgroups / items: per instantiation, the first form_cap of them (items: the targets -- gather form -- or groups --
+ * column-group form -- of an accumulate launch, without the forward-solve workgroups that ride in it and without padding; for
+ * every other instantiation its workgroups); level_riders / level_long: per schedule level
+ * (fgo_stats.n_levels), rider items carried by the level's triangle and row launches / long-list targets of its accumulate launch;
+ * chain2[0]: the backward chain is on, chain2[1]: its mode; names: the instantiations' names, one per line (NUL-terminated).
+ * Any output may be NULL.  Returns the number of instantiations (>= 0) or an error (< 0). */
+int fgo_debug_launch_census(fgo_ctx *ctx, int fused, int64_t *launches, int64_t *workgroups, int64_t *items, int form_cap, int *level_riders,
+                            int *level_long, int level_cap, int *chain2, char *names, int names_cap);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
