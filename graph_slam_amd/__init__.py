@@ -193,6 +193,8 @@ def _load():
     lib.fgo_debug_solve_fused.argtypes = [C.c_void_p, C.c_double, dp]
     lib.fgo_debug_launch_census.argtypes = [C.c_void_p, C.c_int, i64p, i64p, i64p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
                                             C.POINTER(C.c_int), C.c_char_p, C.c_int]
+    lib.fgo_debug_isam_last.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 6 + [C.c_int,
+                                        C.POINTER(C.c_int), C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.c_char_p, dp, C.c_int64]
     lib.fgo_imu_params_vn100.argtypes = [dp]
     lib.fgo_preint_reset.argtypes = [dp, dp]
     lib.fgo_preint_integrate.argtypes = [dp, dp, dp, dp, C.c_double]
@@ -985,6 +987,25 @@ class Graph:
         keys = names.value.decode().split("\n")[:n]
         return dict(forms={k: (int(a), int(w), int(i)) for k, a, w, i in zip(keys, la, wg, it)}, level_riders=[int(v) for v in lr[:nl]],
                     level_long=[int(v) for v in ll[:nl]], chain_on=bool(ch[0]), chain_mode=int(ch[1]))
+
+    def isam2_last(self):
+        """what the last isam2_update ran (fgo_debug_isam_last): dict with 'sweep' (0 full, 1 masked, 2 ranged), 'cut', 'chain_low', per level
+        'level_lo' / 'level_hi' / 'level_ntask' / 'level_fwd' / 'level_fwtab', per task 'task_level' / 'task_dirty' / 'task_run', per variable in the order added
+        'var_task' / 'var_chg' / 'delta' [n, 6]"""
+        ip = C.POINTER(C.c_int)
+        info = np.zeros(5, np.int32)
+        n = self._chk(lib.fgo_debug_isam_last(self._h, info.ctypes.data_as(ip), None, None, None, None, None, 0, None, None, None, 0, None, None, None, 0))
+        nl, nt = int(info[2]), int(info[3])
+        lo = np.zeros(max(nl, 1), np.int32); hi = np.zeros(max(nl, 1), np.int32); cnt = np.zeros(max(nl, 1), np.int32)
+        fw = np.zeros(max(nl, 1), np.int32); ft = np.zeros(max(nl, 1), np.int32)
+        tl = np.zeros(max(nt, 1), np.int32); td = np.zeros(max(nt, 1), np.uint8); tr = np.zeros(max(nt, 1), np.uint8)
+        vt = np.zeros(max(n, 1), np.int32); vc = np.zeros(max(n, 1), np.uint8); de = np.zeros((max(n, 1), 6))
+        cp = lambda a: a.ctypes.data_as(C.c_char_p)
+        self._chk(lib.fgo_debug_isam_last(self._h, info.ctypes.data_as(ip), lo.ctypes.data_as(ip), hi.ctypes.data_as(ip), cnt.ctypes.data_as(ip),
+                                          fw.ctypes.data_as(ip), ft.ctypes.data_as(ip), nl,
+                                          tl.ctypes.data_as(ip), cp(td), cp(tr), nt, vt.ctypes.data_as(ip), cp(vc), _dp(de), n))
+        return dict(sweep=int(info[0]), cut=bool(info[1]), chain_low=int(info[4]), level_lo=lo[:nl], level_hi=hi[:nl], level_ntask=cnt[:nl], level_fwd=fw[:nl], level_fwtab=ft[:nl], task_level=tl[:nt],
+                    task_dirty=td[:nt], task_run=tr[:nt], var_task=vt[:n], var_chg=vc[:n], delta=de[:n])
 
     def bench_phase(self, phase, reps):
         ms = C.c_double()

@@ -301,6 +301,7 @@ struct LaunchCensus {
   // workgroups that ride in the launch and the padding to a multiple of 8; every other form: its workgroups
   int64_t items[LF_COUNT] = {};
   std::vector<int> level_riders, level_long;
+  std::vector<int> level_fwd, level_fwtab;           // per level: forward-role workgroups riding in its accumulate launch; taken from the work-item table
   int chain_on = 0, chain_mode = 0;
   void add(int form, int64_t grid, int64_t n_items = -1) { ++launches[form]; workgroups[form] += grid; items[form] += n_items < 0 ? grid : n_items; }
 };

@@ -193,6 +193,14 @@ struct fgo_ctx {
   std::vector<int64_t> tk_s0, tk_s1, tk_l0, tk_l1;
   std::vector<int> tk_g0, tk_g1, tk_c0, tk_c1, task_level, lvl_lo, lvl_hi;
   bool tk_ok = false;
+  // what the last fgo_isam2_update on this structure ran (debug readers): 0 full sweep, 1 masked (task_dirty, full grids), 2 ranged
+  // (lvl_lo / lvl_hi hold its ranges, isam_set_tasks its dirty tasks); whether its back-substitution was cut (d_bwd_run / d_chg)
+  int isam_last_sweep = 0;
+  bool isam_last_cut = false;
+  fgo::PartialSweep partial_sweep() const {            // the ranged sweep of lvl_lo / lvl_hi over the per-task tables
+    return fgo::PartialSweep{lvl_lo.data(), lvl_hi.data(), tk_s0.data(), tk_s1.data(), tk_l0.data(), tk_l1.data(),
+                             tk_g0.data(), tk_g1.data(), tk_c0.data(), tk_c1.data(), S.task_ptr.data()};
+  }
   // wildfire back-substitution (fgo_isam2_set_wildfire): previous solution in column order, per-task / per-column flags
   double wild_thr = 0;
   bool wild_valid = false;                           // d_xprev holds the solution of the previous update on THIS structure

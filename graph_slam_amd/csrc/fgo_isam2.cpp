@@ -140,7 +140,8 @@ int fgo_isam2_update(fgo_ctx *c, double relin_threshold, fgo_stats *stats) try {
       for (int q = c->S.task_ptr[t]; q < c->S.task_ptr[t + 1]; ++q) { const int k = c->S.task_cols[q]; if (!col_dirty[k]) { col_dirty[k] = 1; set_cols.push_back(k); } }
     // when most of the tree is affected (a relinearisation wave after a loop closure) the full sweep is the faster one:
     // the flag look-ups cost every workgroup two extra dependent loads
-    if (n_dirty_tasks > (int64_t)(0.3 * ntask)) n_dirty_tasks = -2;
+    static const double full_frac = tune("isam_full_frac", 0.3);
+    if (n_dirty_tasks > (int64_t)(full_frac * ntask)) n_dirty_tasks = -2;
     if (n_dirty_tasks >= 0) {
       HIPCHK(c, hipMemcpyAsync(c->d_task_dirty.p, task_dirty, (size_t)ntask, hipMemcpyHostToDevice, s));
       HIPCHK(c, hipMemcpyAsync(c->d_col_dirty.p, col_dirty, (size_t)nb, hipMemcpyHostToDevice, s));
@@ -172,9 +173,9 @@ int fgo_isam2_update(fgo_ctx *c, double relin_threshold, fgo_stats *stats) try {
       for (int l = 0; l < nl; ++l) std::fprintf(stderr, " %d/%d", c->lvl_hi[(size_t)l] < c->lvl_lo[(size_t)l] ? 0 : c->lvl_hi[(size_t)l] - c->lvl_lo[(size_t)l] + 1, c->sched.level_ptr[l + 1] - c->sched.level_ptr[l]);
       std::fprintf(stderr, "\n");
     }
-    ps = PartialSweep{c->lvl_lo.data(), c->lvl_hi.data(), c->tk_s0.data(), c->tk_s1.data(), c->tk_l0.data(), c->tk_l1.data(),
-                      c->tk_g0.data(), c->tk_g1.data(), c->tk_c0.data(), c->tk_c1.data(), c->S.task_ptr.data()};
+    ps = c->partial_sweep();
   }
+  c->isam_last_sweep = !plan.task_dirty ? 0 : ranged ? 2 : 1;   // (fgo_debug_launch_census / fgo_debug_isam_last walk and read this sweep)
   launch_factor(plan, c->sched, c->d_H[w].p, c->d_L.p, scal + 3, c->d_fail.p, s, c->d_b[w].p, c->d_x.p, PHASE_ALL, ranged ? &ps : nullptr);
   if (have_tables) launch_copy_vec(c->d_x.p, c->d_y.p, (int64_t)c->plan.nb * 6, s);       // y for the next step
   st.reserved[3] = (double)n_dirty_tasks;               // tasks re-run by this step (-1: full sweep, -2: full sweep because most of the tree was affected)
@@ -188,6 +189,7 @@ int fgo_isam2_update(fgo_ctx *c, double relin_threshold, fgo_stats *stats) try {
   const bool wild_possible = c->wild_thr > 0 && have_tables && c->d_xprev.p && c->sched.bchain_low >= 0;
   if (wild_possible) launch_copy_vec(c->d_x.p, c->d_xprev.p, (int64_t)c->plan.nb * 6, s);
   st.reserved[4] = wild ? 1.0 : 0.0;                    // this update cut its back-substitution (wildfire)
+  c->isam_last_cut = wild;
   if (std::getenv("FGO_ISAM_DEBUG"))
     std::fprintf(stderr, "[isam] wildfire: thr %g, partial %d, solution of the previous update kept %d, backward chain from level %d (%d panels) -> cut %d\n",
                  c->wild_thr, plan.task_dirty != nullptr, (int)c->wild_valid, c->sched.bchain_low, c->sched.bchain_n, (int)wild);

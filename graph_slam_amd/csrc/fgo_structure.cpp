@@ -1043,6 +1043,7 @@ struct StructureBuild {
     HIPCHK(c, c->d_bwd_run.alloc((size_t)ntask));
     HIPCHK(c, c->d_chg.alloc((size_t)nb));
     c->wild_valid = false;
+    c->isam_last_sweep = 0; c->isam_last_cut = false;
     c->isam_moved_valid = false;                    // (the flags of the previous update were laid out for the previous structure)
     c->isam_H_valid = false;
     HIPCHK(c, c->d_y.alloc((size_t)nb * 6));

@@ -1882,7 +1882,7 @@ __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_fused(DevPlan P, const doub
   __shared__ __attribute__((aligned(16))) double sb[16 * NJMAX], wb[16 * NJMAX], xb[16 * NJMAX];
   const int pn = pn0 + blockIdx.x;
   const PanelDesc d = P.pp.pdesc[pn];
-  if (!task_runs(P, d.task)) return;                       // (backward sweeps always run whole; kept for symmetry)
+  if (!task_runs(P, d.task)) return;                       // (the wildfire mask: launch_solve passes task_dirty = run, k_wild_mark restores x of a task left out)
   const int m = d.m, n = 6 * m, nJ = (n + 15) >> 4;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane / 6, cc = lane - 6 * g;
@@ -2442,7 +2442,7 @@ void launch_factor(const DevPlan &P, const HostSchedule &H, const double *Hblk, 
                    int *fail_flag, hipStream_t s, const double *b, double *x, int phase, const PartialSweep *ps, const double *b_full, LaunchCensus *cz) {
   // (partial sweep, P.task_dirty set: the caller has prepared x = b on the dirty columns and the saved y elsewhere)
   if (x && phase != PHASE_TOP && !P.task_dirty && !cz) launch_copy(b, x, (int64_t)P.top_col0 * 6, s);   // (the top of x is written by k_dist_rhs when distributed)
-  if (cz) { cz->level_riders.assign((size_t)H.n_levels, 0); cz->level_long.assign((size_t)H.n_levels, 0); }
+  if (cz) { cz->level_riders.assign((size_t)H.n_levels, 0); cz->level_long.assign((size_t)H.n_levels, 0); cz->level_fwd.assign((size_t)H.n_levels, 0); cz->level_fwtab.assign((size_t)H.n_levels, 0); }
   for (int l = 0; l < H.n_levels; ++l) {
     if (!seg_runs(H, l, phase)) continue;
     const int64_t a0 = H.acc_ptr[l], am = H.acc_mid[l], a1 = H.acc_ptr[l + 1];
@@ -2462,6 +2462,7 @@ void launch_factor(const DevPlan &P, const HostSchedule &H, const double *Hblk, 
       else if (!fw_table) { col0 = ps->task_ptr[ta]; n_fwd_wg = ps->task_ptr[tb + 1] - ps->task_ptr[ta]; }
     }
     const int grid = n_acc_wg + n_long + n_fwd_wg;
+    if (cz) { cz->level_fwd[(size_t)l] = n_fwd_wg; cz->level_fwtab[(size_t)l] = (fw_table && n_fwd_wg > 0) ? 1 : 0; }
     const int n_g2_full = H.g2_lvl.empty() ? 0 : (int)(H.g2_lvl[l + 1] - H.g2_lvl[l]);
     const int64_t g2f = (!ps || n_g2_full == 0) ? (H.g2_lvl.empty() ? 0 : H.g2_lvl[l]) : (nothing_dirty ? H.g2_lvl[l] : ps->g0[ta]);
     const int n_g2 = (!ps || n_g2_full == 0) ? n_g2_full : (nothing_dirty ? 0 : ps->g1[tb] - ps->g0[ta]);

@@ -686,12 +686,26 @@ int fgo_debug_solve_fused(fgo_ctx *ctx, double lambda, double *delta_out);
  * are walked with their launches switched off).  fused != 0: as fgo_debug_solve_fused / an LM trial, 0: as fgo_solve_step.
  * launches / workgroups / items: per instantiation, the first form_cap of them (items: the targets -- gather form -- or groups --
  * column-group form -- of an accumulate launch, without the forward-solve workgroups that ride in it and without padding; for
- * every other instantiation its workgroups); level_riders / level_long: per schedule level
+ * every other instantiation its workgroups); fused == 2: the factor sweep as the last fgo_isam2_update ran it; level_riders / level_long: per schedule level
  * (fgo_stats.n_levels), rider items carried by the level's triangle and row launches / long-list targets of its accumulate launch;
  * chain2[0]: the backward chain is on, chain2[1]: its mode; names: the instantiations' names, one per line (NUL-terminated).
  * Any output may be NULL.  Returns the number of instantiations (>= 0) or an error (< 0). */
 int fgo_debug_launch_census(fgo_ctx *ctx, int fused, int64_t *launches, int64_t *workgroups, int64_t *items, int form_cap, int *level_riders,
                             int *level_long, int level_cap, int *chain2, char *names, int names_cap);
+/* tests: what the last fgo_isam2_update on this context ran.  info5: {sweep (0 full, 1 masked: dirty flags on full grids, 2 ranged),
+ * back-substitution cut (0 / 1), schedule levels, tasks, first level of the backward chain (-1: none)}.  Per level (the first level_cap): the task range [lo, hi] the factor sweep
+ * launched (hi < lo: none; the whole level unless the sweep was ranged), the level's task count, the forward-solve workgroups
+ * that rode in its accumulate launch and whether they came from the level's work-item table (both as the launcher itself records them).  Per task (the first task_cap):
+ * its level, whether it was re-factored, and -- after a cut back-substitution -- whether it was solved again (1 for every task
+ * otherwise, and for the tasks of the backward chain, which are always solved).  Per variable, in the order the variables were
+ * added, phantom slots left out (the first var_cap): its task (-1: fixed), whether the cut found its delta moved by >= the
+ * wildfire threshold (0 when nothing was cut), and its delta (6 doubles).  Any output may be NULL.  fgo_debug_launch_census with
+ * fused == 2 walks the factor sweep of the same update (FGO_ESTATE if it was a full sweep).  Returns the number of variables the
+ * ISAM2 state covers (>= 0) or an error (< 0); FGO_ESTATE before the first update / after a change of structure. */
+int fgo_debug_isam_last(fgo_ctx *ctx, int *info5, int *level_lo, int *level_hi, int *level_ntask, int *level_fwd, int *level_fwtab, int level_cap,
+                        int *task_level,
+                        unsigned char *task_dirty, unsigned char *task_run, int task_cap, int *var_task, unsigned char *var_chg,
+                        double *var_delta, int64_t var_cap);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

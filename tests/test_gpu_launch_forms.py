@@ -94,13 +94,19 @@ KAPPA = 8.0 * 1.113e-3
 EPS = 2.0 ** -53
 
 
-def _run_child(name, tune, out_dir, dense, timeout):
+def _stops(rc):
+    """the stop rule: after a child that ended with a signal, an abort, a segmentation fault, a device error or its timeout no further
+    child is started"""
+    return rc == "timeout" or rc < 0 or rc in (3, 134, 139)
+
+
+def _run_child(name, tune, out_dir, dense, timeout, child=CHILD, args=()):
     env = dict(os.environ)
     if tune:
         env["FGO_TUNE"] = tune
     else:
         env.pop("FGO_TUNE", None)
-    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [CHILD, "--out", out_dir] + (["--dense"] if dense else [])
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [child, "--out", out_dir] + (["--dense"] if dense else []) + list(args)
     t0 = time.time()
     try:
         r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
@@ -127,8 +133,7 @@ def runs(tmp_path_factory):
         run = _run_child(name, tune, str(base / name), name == "default", limit)
         out[name] = run
         print("[launch forms] set %-10s rc %s  %.1f s" % (name, run["rc"], run["seconds"]))
-        rc = run["rc"]
-        if rc == "timeout" or rc < 0 or rc in (3, 134, 139):       # signal, abort, segmentation fault, device error, timeout
+        if _stops(run["rc"]):
             stopped = name
         if name == "default":
             limit = max(60.0, 10.0 * run["seconds"])                # sized from the measured time of the default set
