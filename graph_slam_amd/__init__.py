@@ -195,6 +195,7 @@ def _load():
                                             C.POINTER(C.c_int), C.c_char_p, C.c_int]
     lib.fgo_debug_isam_last.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 6 + [C.c_int,
                                         C.POINTER(C.c_int), C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.c_char_p, dp, C.c_int64]
+    lib.fgo_debug_linearize_census.argtypes = [C.c_void_p, i64p]
     lib.fgo_imu_params_vn100.argtypes = [dp]
     lib.fgo_preint_reset.argtypes = [dp, dp]
     lib.fgo_preint_integrate.argtypes = [dp, dp, dp, dp, C.c_double]
@@ -1006,6 +1007,15 @@ class Graph:
                                           tl.ctypes.data_as(ip), cp(td), cp(tr), nt, vt.ctypes.data_as(ip), cp(vc), _dp(de), n))
         return dict(sweep=int(info[0]), cut=bool(info[1]), chain_low=int(info[4]), level_lo=lo[:nl], level_hi=hi[:nl], level_ntask=cnt[:nl], level_fwd=fw[:nl], level_fwtab=ft[:nl], task_level=tl[:nt],
                     task_dirty=td[:nt], task_run=tr[:nt], var_task=vt[:n], var_chg=vc[:n], delta=de[:n])
+
+    LINEARIZE_CENSUS = ("n_hubs", "n_hub_vars", "n_hub_multi", "hub_deg", "hub_cap", "n_dup_groups", "n_dup_members", "n_priors",
+                        "n_phantom", "imu_ncolor", "maskable", "structure_rebuilt")
+
+    def linearize_census(self):
+        """what the next linearisation launches (fgo_debug_linearize_census; nothing runs): dict of the counts in LINEARIZE_CENSUS"""
+        out = np.zeros(12, np.int64)
+        self._chk(lib.fgo_debug_linearize_census(self._h, _i64p(out)))
+        return {k: int(v) for k, v in zip(self.LINEARIZE_CENSUS, out)}
 
     def bench_phase(self, phase, reps):
         ms = C.c_double()

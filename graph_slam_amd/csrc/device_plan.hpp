@@ -74,9 +74,11 @@ struct RideItem;
 
 constexpr int EDGE_REC = 32;    // doubles per edge record (256 B = two 128-byte lines)
 // Linearisation hubs.  A variable with many half-edges would serialise its factor evaluations on the 4 lanes it normally
-// gets; above DevPlan::hub_deg it is linearised by whole 256-thread workgroups instead, one per SLICE of HUB_SLICE
-// half-edges (a plane seen from 50 000 keyframes: 25 workgroups, 8 evaluations per thread), the slices' partial sums
-// combined in a fixed order by k_hub_combine*.  hub_deg is chosen per graph (fgo_api.cpp plan_hubs): the smallest of
+// gets; above DevPlan::hub_deg it is linearised by whole 256-thread workgroups instead: n = min(HUB_MAX_SLICES,
+// ceil(degree / HUB_SLICE)) of them ("slices"), which stride through the variable's list TOGETHER -- thread t of slice q takes
+// the half-edges q * 256 + t, + 256 n, ... (513 half-edges: two slices, two evaluations on thread 0 of slice 0, one on every
+// other thread; a plane seen from 50 000 keyframes: 64 workgroups, 3 - 4 evaluations per thread) -- the slices' partial sums
+// combined in a fixed order by k_hub_combine*.  hub_deg is chosen per graph (fgo_structure.cpp plan_hubs): the smallest of
 // 64 .. 1024 that leaves at most HUB_MAX_VARS hub variables -- a few hundred planes seen from everywhere become hubs at
 // 64; the 10 000 cameras of a bundle adjustment (~500 observations each, plenty of them to fill the chip) stay on the
 // 4-lane path, which measured faster for them.

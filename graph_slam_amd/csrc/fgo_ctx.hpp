@@ -246,6 +246,12 @@ struct fgo_ctx {
   int imu_extra = 0;
   fgo::DevBuf<double> d_stage;
   int64_t n_priors_dev = 0;
+  // what fgo_debug_linearize_census reports beside the plan's own counts (kept by upload_hubs / the duplicate-group uploads / the
+  // end of either structure phase)
+  int n_hub_vars = 0;               // distinct hub variables behind the plan's n_hubs entries
+  size_t hub_entry_cap = 0;         // hub entries the scratch buffers hold
+  int64_t n_dup_members = 0;        // factors in the plan's n_dup_groups duplicate groups
+  int last_phase_rebuilt = 1;       // the last structure phase: 1 build(), 0 refresh_factors() in place
   hipGraphExec_t trial_graph[2] = {nullptr, nullptr};
   hipEvent_t ev[6] = {};
   double *h_scal = nullptr;         // pinned: [0] chi2 cur, [1] scale, [2] maxdiag, [3] lambda, [4] chi2 cand

@@ -196,6 +196,22 @@ int fgo_debug_launch_census(fgo_ctx *c, int fused, int64_t *launches, int64_t *w
   return LF_COUNT;
 } FGO_CATCH_INT(c)
 
+// tests: what the next linearisation of this context launches (see include/fgo.h).  Counts only: nothing is launched, nothing is
+// read from the device
+int fgo_debug_linearize_census(fgo_ctx *c, int64_t out[12]) try {
+  if (!c || !out) return FGO_EINVAL;
+  (void)hipSetDevice(c->cfg.device);
+  int rc = ensure_ready(c);
+  if (rc) return rc;
+  const DevPlan &P = c->plan;
+  out[0] = P.n_hubs; out[1] = c->n_hub_vars; out[2] = P.n_hub_multi; out[3] = P.hub_deg; out[4] = (int64_t)c->hub_entry_cap;
+  out[5] = P.n_dup_groups; out[6] = c->n_dup_members;
+  out[7] = P.n_priors; out[8] = c->n_phantom; out[9] = P.imu_ncolor;
+  out[10] = c->gtsam_mode && linearize_gtsam_maskable(P) ? 1 : 0;
+  out[11] = c->last_phase_rebuilt;
+  return FGO_OK;
+} FGO_CATCH_INT(c)
+
 // tests: what the last fgo_isam2_update on this context ran (see include/fgo.h)
 int fgo_debug_isam_last(fgo_ctx *c, int *info5, int *level_lo, int *level_hi, int *level_ntask, int *level_fwd, int *level_fwtab, int level_cap, int *task_level, unsigned char *task_dirty,
                         unsigned char *task_run, int task_cap, int *var_task, unsigned char *var_chg, double *var_delta, int64_t var_cap) try {

@@ -923,6 +923,7 @@ struct StructureBuild {
   HIPCHK(c, c->d_dup_ptr.upload(dup_ptr, s));
   HIPCHK(c, c->d_dup_edges.upload(dup_edges, s));
   HIPCHK(c, c->d_dup_slot.upload(dup_slot, s));
+  c->n_dup_members = (int64_t)dup_edges.size();
   HIPCHK(c, c->d_ainv.upload(erec, s));
   { const int rc = upload_priors(c, NX, var_mine); if (rc) return rc; }
   NP = c->n_priors_dev;
@@ -1451,6 +1452,7 @@ struct StructureBuild {
     fgo_stats &st = c->last;
     std::memset(&st, 0, sizeof(st));
     st.structure_rebuilt = 1;
+    c->last_phase_rebuilt = 1;
     st.t_symbolic = t1 - t0;
     st.t_upload = now_s() - t1;
     st.n_free = nb - (int)R + n_lm; st.n_edges = E;         // the phantom slots of the incremental mode are not the caller's variables
@@ -1529,12 +1531,17 @@ static int upload_hubs(fgo_ctx *c, const HubPlan &hp, size_t entry_cap) {
   }
   if (!hp.multi.empty()) HIPCHK(c, hipMemcpyAsync(c->d_hubm.p, hp.multi.data(), sizeof(int) * hp.multi.size(), hipMemcpyHostToDevice, s));
   HIPCHK(c, hipStreamSynchronize(s));        // the caller's HubPlan may die right after
+  c->hub_entry_cap = std::max(entry_cap, hp.var.size());
+  c->n_hub_vars = 0;
+  for (const int sl : hp.slice) c->n_hub_vars += (sl & 0xffff) == 0;
   return FGO_OK;
 }
 
-// Incremental mode: the graph grew since the structure was built.  If the new variables fit the phantom slots and every
-// new factor couples variables whose pair already exists in the structure, the factor-side device arrays are extended
-// in place: returns FGO_OK (done), 1 (does not fit: the caller rebuilds), or an error.
+// Incremental mode: the graph grew since the structure was built.  If the new variables fit the phantom slots, every
+// new factor couples variables whose pair already exists in the structure (a fixed end needs none), the factors fit the
+// capacities laid down at the build and the hub entries of the extended graph fit hub_cap, the factor-side device arrays are
+// extended in place: returns FGO_OK (done), 1 (does not fit: the caller rebuilds), or an error.  DESIGN.md "Growing graphs" has
+// the table; tests/test_gpu_growth_forms.py holds its rows on variables, factors, duplicates, hubs and priors to H / b.
 int refresh_factors(fgo_ctx *c) {
   fgo_ctx::Incr &I = c->inc;
   const bool growing = c->gtsam_mode ? c->isam_incremental : c->grow_incremental;
@@ -1622,6 +1629,7 @@ int refresh_factors(fgo_ctx *c) {
   HIPCHK(c, c->d_dup_ptr.upload(dup_ptr, s));
   HIPCHK(c, c->d_dup_edges.upload(dup_edges, s));
   HIPCHK(c, c->d_dup_slot.upload(dup_slot, s));
+  c->n_dup_members = (int64_t)dup_edges.size();
   const int64_t dE = E - I.E_done;
   std::vector<double> stage((size_t)28 * dE);
   if (dE > 0) {
@@ -1737,6 +1745,7 @@ int refresh_factors(fgo_ctx *c) {
   drop_undamped(c);
   fgo_stats &st = c->last;
   st.structure_rebuilt = 0;
+  c->last_phase_rebuilt = 0;
   st.t_symbolic = now_s() - t0;                                 // host time of the in-place extension
   st.t_upload = 0;
   st.n_edges = E;

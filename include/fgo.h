@@ -706,6 +706,13 @@ int fgo_debug_isam_last(fgo_ctx *ctx, int *info5, int *level_lo, int *level_hi, 
                         int *task_level,
                         unsigned char *task_dirty, unsigned char *task_run, int task_cap, int *var_task, unsigned char *var_chg,
                         double *var_delta, int64_t var_cap);
+/* tests: what the next linearisation of this context launches, as counts copied from the context and its device plan (the structure
+ * is brought up to date first, as by every other call; nothing is launched).  out[0..11]: hub entries (one workgroup each), distinct
+ * hub variables, hubs of more than one slice (what k_hub_combine* runs on), the degree above which a variable is a hub, hub entries
+ * the scratch buffers hold; duplicate groups and the factors in them; unary priors on the device; unclaimed phantom slots of the
+ * growth reserve; colour slots of the IMU factors (64 + the factors with a colour of their own); whether the masked ISAM2 linearisation applies (GTSAM
+ * semantics only); whether the last structure phase was a build (1) or an in-place extension (0). */
+int fgo_debug_linearize_census(fgo_ctx *ctx, int64_t out[12]);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

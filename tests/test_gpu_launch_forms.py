@@ -97,16 +97,16 @@ EPS = 2.0 ** -53
 def _stops(rc):
     """the stop rule: after a child that ended with a signal, an abort, a segmentation fault, a device error or its timeout no further
     child is started"""
-    return rc == "timeout" or rc < 0 or rc in (3, 134, 139)
+    return rc == "timeout" or rc < 0 or rc in (3, 124, 134, 137, 139)        # (124 / 137: ended by a `timeout -k` in front of the child)
 
 
-def _run_child(name, tune, out_dir, dense, timeout, child=CHILD, args=()):
+def _run_child(name, tune, out_dir, dense, timeout, child=CHILD, args=(), prefix=()):
     env = dict(os.environ)
     if tune:
         env["FGO_TUNE"] = tune
     else:
         env.pop("FGO_TUNE", None)
-    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [child, "--out", out_dir] + (["--dense"] if dense else []) + list(args)
+    cmd = list(prefix) + [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [child, "--out", out_dir] + (["--dense"] if dense else []) + list(args)
     t0 = time.time()
     try:
         r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
