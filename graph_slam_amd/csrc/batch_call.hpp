@@ -1,0 +1,85 @@
+// Host-side plumbing shared by the stand-alone fgo_*_batch entry points (two-view BA, plane check, IMU check, VRO RANSAC, plane
+// extraction): input validators, device selection, and the one device allocation a call stages its arrays in.  An entry point
+// decides every FGO_EINVAL, and n == 0 -> FGO_OK, with the validators alone, before select_device() makes the first HIP call.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <cassert>
+#include <cmath>
+#include "../../include/fgo.h"
+
+namespace fgo {
+
+// a quaternion that can be normalised: its squared norm is positive and finite
+inline bool quat_ok(const double *q) {
+  const double qq = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+  return qq > 0 && std::isfinite(qq);
+}
+// a ptr array (n rows, n + 1 entries) is non-negative and non-decreasing, and no row holds more than max_per_row entries
+inline bool csr_ptr_ok(const int64_t *ptr, int64_t n, int64_t max_per_row) {
+  if (ptr[0] < 0) return false;
+  for (int64_t r = 0; r < n; ++r)
+    if (ptr[r + 1] < ptr[r] || ptr[r + 1] - ptr[r] > max_per_row) return false;
+  return true;
+}
+
+inline int select_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FGO_ENODEV;   // no CPU fallback
+  if (hipSetDevice(device) != hipSuccess) return FGO_ENODEV;
+  return FGO_OK;
+}
+
+// Every device array of a call lives in ONE allocation: a call costs one hipMalloc / hipFree whatever it asks for.  reserve() hands
+// out offsets (256-byte aligned) before the allocation is made, at() turns them into pointers afterwards.
+struct Arena {
+  char *base = nullptr;
+  size_t total = 0;
+  ~Arena() { if (base) (void)hipFree(base); }
+  size_t reserve(size_t bytes) { const size_t o = total; total += (bytes + 255) & ~(size_t)255; return o; }
+  hipError_t alloc() { return hipMalloc((void **)&base, total ? total : 1); }
+  template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(base + off); }
+};
+
+// the pair of events around a launch whose kernel time a debug hook reports
+struct Events {
+  hipEvent_t a = nullptr, b = nullptr;
+  ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+};
+
+// The arrays of a call, staged in one Arena in the order they are named.  in() names an array that upload() copies to the device,
+// out() one that download() copies back; both return a handle for ptr().  An array whose host pointer is NULL is absent -- nothing
+// is reserved and ptr() gives NULL -- unless out() is told `always`: the device side is then there for the kernel to work in
+// (scratch, or an output the kernel needs whether or not the caller wants it) and only the copy back is skipped.
+struct Staged {
+  static constexpr int CAP = 16;
+  struct Entry { const void *src; void *dst; size_t bytes, off; bool present; };
+  Arena mem;
+  Entry e[CAP];
+  int n = 0;
+
+  int in(const void *host, size_t bytes) { return add({host, nullptr, bytes, 0, host != nullptr}); }
+  int out(void *host, size_t bytes, bool always = false) { return add({nullptr, host, bytes, 0, host != nullptr || always}); }
+  int alloc() { return mem.alloc() == hipSuccess ? FGO_OK : FGO_ENOMEM; }
+  int upload() const {
+    for (int k = 0; k < n; ++k)
+      if (e[k].src && e[k].bytes && hipMemcpy(mem.base + e[k].off, e[k].src, e[k].bytes, hipMemcpyHostToDevice) != hipSuccess) return FGO_ENUM;
+    return FGO_OK;
+  }
+  int download() const {
+    for (int k = 0; k < n; ++k)
+      if (e[k].dst && e[k].bytes && hipMemcpy(e[k].dst, mem.base + e[k].off, e[k].bytes, hipMemcpyDeviceToHost) != hipSuccess) return FGO_ENUM;
+    return FGO_OK;
+  }
+  template <class T> T *ptr(int h) const { return e[h].present ? mem.at<T>(e[h].off) : nullptr; }
+
+ private:
+  int add(Entry x) {
+    assert(n < CAP);
+    if (x.present) x.off = mem.reserve(x.bytes);
+    e[n] = x;
+    return n++;
+  }
+};
+
+}  // namespace fgo

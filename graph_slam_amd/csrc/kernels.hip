@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include "fgo_internal.hpp"
 #include "se3_device.hpp"
+#include "small_dense_device.hpp"
 
 namespace fgo {
 using namespace dev;
@@ -29,17 +30,6 @@ using namespace dev;
 constexpr int PM = PANEL_MAX;
 constexpr int NJMAX = (6 * PM + 15) / 16;              // 16-wide tile rows of a panel's dense scalar triangle (6 / 12)
 typedef double d4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, WAVE));
-  return v;
-}
 
 // block-level deterministic sum: wave shuffles, then LDS across waves (fixed order)
 template <int NW>

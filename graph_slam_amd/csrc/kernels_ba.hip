@@ -18,17 +18,12 @@
 #include "device_plan.hpp"
 #include "fgo_internal.hpp"
 #include "factors_device.hpp"
+#include "small_dense_device.hpp"
 
 namespace fgo {
 using namespace dev;
 
 namespace {
-__device__ __forceinline__ double wsum_ba(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void k_ba_linearize(DevPlan P, const double *__restrict__ vals,
                                                       double *__restrict__ Hpp, double *__restrict__ bp, double *__restrict__ bvec,
                                                       double *__restrict__ chi_partial) {
@@ -79,7 +74,7 @@ __global__ __launch_bounds__(256) void k_ba_linearize(DevPlan P, const double *_
     double *__restrict__ bv = bvec + 6 * ((int64_t)P.nb + p);         // the gradient of the virtual column (gain-ratio model)
     bv[0] = g0; bv[1] = g1; bv[2] = g2; bv[3] = 0; bv[4] = 0; bv[5] = 0;
   }
-  chi = wsum_ba(chi);
+  chi = wave_sum(chi);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = chi;
   __syncthreads();
   if (threadIdx.x == 0) chi_partial[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
@@ -402,9 +397,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     __builtin_amdgcn_wave_barrier();
   }
 #pragma unroll
-  for (int k = 0; k < 21; ++k) h[k] = wsum_ba(h[k]);
+  for (int k = 0; k < 21; ++k) h[k] = wave_sum(h[k]);
 #pragma unroll
-  for (int k = 0; k < 6; ++k) gv[k] = wsum_ba(gv[k]);
+  for (int k = 0; k < 6; ++k) gv[k] = wave_sum(gv[k]);
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < 21; ++k) red[wave][k] = h[k];

@@ -15,6 +15,7 @@
 #include <stdint.h>
 #include "device_plan.hpp"
 #include "pose3_device.hpp"
+#include "small_dense_device.hpp"
 
 namespace fgo {
 using namespace dev;
@@ -25,7 +26,7 @@ constexpr int GATE_G = 10;                     // lane groups of 6 in the one-wa
 constexpr int GATE_LDS = 150;                  // doubles per group: Ja (later Y = P L), Jb, L, M (36 each), w (6)
 
 __device__ __forceinline__ constexpr int ut(int r, int c) {      // index of (r, c) in the 21 upper-triangular entries, row-major
-  return r <= c ? r * 6 - r * (r - 1) / 2 + (c - r) : c * 6 - c * (c - 1) / 2 + (r - c);
+  return r <= c ? ut6(r, c) : ut6(c, r);
 }
 
 // lower Cholesky factor of the symmetric matrix whose lower triangle is a(i, j); false if a pivot is not positive (NaN included):

@@ -12,18 +12,14 @@
 #include "device_plan.hpp"
 #include "factors_device.hpp"
 #include "imu_device.hpp"
+#include "small_dense_device.hpp"
 
 namespace fgo {
 using namespace dev;
 
 namespace {
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ double bsum4(double v, double *sh) {
-  v = wsum(v);
+  v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
   __syncthreads();
   const double s = sh[0] + sh[1] + sh[2] + sh[3];
@@ -595,7 +591,7 @@ __global__ __launch_bounds__(64) void k_chi2_imu(DevPlan P, const double *__rest
     for (int a = 0; a < 15; ++a)
       for (int b = 0; b < 15; ++b) chi += r[a] * m.info[a * 15 + b] * r[b];
   }
-  chi = wsum(chi);
+  chi = wave_sum(chi);
   if (threadIdx.x == 0) chi_partial[blockIdx.x] = chi;
 }
 

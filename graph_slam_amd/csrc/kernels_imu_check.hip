@@ -25,6 +25,8 @@
 #include <cmath>
 #include "../../include/fgo.h"
 #include "pose3_device.hpp"
+#include "small_dense_device.hpp"
+#include "batch_call.hpp"
 
 namespace fgo {
 using namespace dev;
@@ -42,9 +44,6 @@ struct IcArgs {
   double *dw, *cov_dw;                             // may be NULL
 };
 
-__device__ __forceinline__ constexpr int lt(int r, int c) { return r * (r + 1) / 2 + c; }           // lower triangle packed by rows
-__device__ __forceinline__ constexpr int ut(int r, int c) { return r * 6 - r * (r - 1) / 2 + c - r; }   // upper triangle of a 6x6, by rows
-
 // the LDS traffic of one wave: orders this wave's LDS accesses around the point for the compiler and the hardware
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -52,54 +51,12 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// the leading 3x3 block (s00 s01 s02 s11 s12 s22) of A^-1 for the symmetric 6x6 A given by its upper triangle, through the
-// Cholesky factor A = L L^T and L^-1; false if a pivot is <= 0 or not finite (the factor then carries a unit pivot there)
+// the leading 3x3 block (s00 s01 s02 s11 s12 s22) of A^-1 for the symmetric 6x6 A given by its upper triangle; false if a pivot is
+// <= 0 or not finite.  The part of inv6 that these six entries do not need is never computed.
 __device__ __forceinline__ bool inv6_lead3(const double *__restrict__ a_ut, double S[6]) {
-  double a[21];
-#pragma unroll
-  for (int r = 0; r < 6; ++r)
-#pragma unroll
-    for (int c = 0; c <= r; ++c) a[lt(r, c)] = a_ut[ut(c, r)];
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double d = a[lt(j, j)];
-#pragma unroll
-    for (int k = 0; k < j; ++k) d -= a[lt(j, k)] * a[lt(j, k)];
-    const bool okj = d > 0 && d < __builtin_huge_val();
-    ok = ok && okj;
-    const double l = sqrt(okj ? d : 1.0);
-    a[lt(j, j)] = l;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double s = a[lt(i, j)];
-#pragma unroll
-      for (int k = 0; k < j; ++k) s -= a[lt(i, k)] * a[lt(j, k)];
-      a[lt(i, j)] = s / l;
-    }
-  }
-  double Mi[21];                                   // L^-1, lower, packed by rows; columns 0 .. 2 are all that is read
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    Mi[lt(c, c)] = 1.0 / a[lt(c, c)];
-#pragma unroll
-    for (int r = c + 1; r < 6; ++r) {
-      double s = 0;
-#pragma unroll
-      for (int k = c; k < r; ++k) s += a[lt(r, k)] * Mi[lt(k, c)];
-      Mi[lt(r, c)] = -s / a[lt(r, r)];
-    }
-  }
-  int o = 0;
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = r; c < 3; ++c) {                  // A^-1 = L^-T L^-1
-      double s = 0;
-#pragma unroll
-      for (int k = c; k < 6; ++k) s += Mi[lt(k, r)] * Mi[lt(k, c)];
-      S[o++] = s;
-    }
+  double Si[21];
+  const bool ok = inv6(a_ut, Si);
+  S[0] = Si[ut6(0, 0)]; S[1] = Si[ut6(0, 1)]; S[2] = Si[ut6(0, 2)]; S[3] = Si[ut6(1, 1)]; S[4] = Si[ut6(1, 2)]; S[5] = Si[ut6(2, 2)];
   return ok;
 }
 
@@ -153,7 +110,7 @@ __global__ __launch_bounds__(64) void k_imu_check(IcArgs A) {
     bool ok = true;
     for (int j = 0; j < 15; ++j) {
       const double d = L[j * 16];                  // every lane reads the pivot before lane j replaces it: ok stays wave-uniform
-      const bool okj = d > 0 && d < __builtin_huge_val();
+      const bool okj = pivot_ok(d);
       ok = ok && okj;
       const double l = sqrt(okj ? d : 1.0);
       wave_sync();
@@ -200,13 +157,13 @@ __global__ __launch_bounds__(64) void k_imu_check(IcArgs A) {
     // d2 = dw^T S^-1 dw
     {
       const double a00 = S.m[0], a10 = S.m[3], a11 = S.m[4], a20 = S.m[6], a21 = S.m[7], a22 = S.m[8];
-      const bool ok0 = a00 > 0 && a00 < __builtin_huge_val();
+      const bool ok0 = pivot_ok(a00);
       const double l00 = sqrt(ok0 ? a00 : 1.0), l10 = a10 / l00, l20 = a20 / l00;
       const double s1 = a11 - l10 * l10;
-      const bool ok1 = s1 > 0 && s1 < __builtin_huge_val();
+      const bool ok1 = pivot_ok(s1);
       const double l11 = sqrt(ok1 ? s1 : 1.0), l21 = (a21 - l20 * l10) / l11;
       const double s2 = a22 - l20 * l20 - l21 * l21;
-      const bool ok2 = s2 > 0 && s2 < __builtin_huge_val();
+      const bool ok2 = pivot_ok(s2);
       const double l22 = sqrt(ok2 ? s2 : 1.0);
       const double y0 = dw.x / l00, y1 = (dw.y - l10 * y0) / l11, y2 = (dw.z - l20 * y0 - l21 * y1) / l22;
       d2 = y0 * y0 + y1 * y1 + y2 * y2;
@@ -230,21 +187,6 @@ __global__ __launch_bounds__(64) void k_imu_check(IcArgs A) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) o[k] = S.m[k];
   }
-}
-
-// Every device array of a call lives in ONE allocation: a call costs one hipMalloc / hipFree whatever it asks for.  reserve() hands
-// out offsets (256-byte aligned) before the allocation is made, at() turns them into pointers afterwards.
-struct Arena {
-  char *base = nullptr;
-  size_t total = 0;
-  ~Arena() { if (base) (void)hipFree(base); }
-  size_t reserve(size_t bytes) { const size_t o = total; total += (bytes + 255) & ~(size_t)255; return o; }
-  hipError_t alloc() { return hipMalloc((void **)&base, total ? total : 1); }
-  template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(base + off); }
-};
-bool quat_ok(const double *q) {
-  const double qq = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
-  return qq > 0 && std::isfinite(qq);
 }
 
 }  // namespace
@@ -272,42 +214,27 @@ extern "C" int fgo_imu_check_vro_batch(int device, int64_t n_records, const doub
   if (n_preint < 1 || (uint64_t)n_preint > SIZE_MAX / sizeof(fgo_preint)) return FGO_EINVAL;
   for (int64_t r = 0; r < n_records; ++r)
     if (preint_index[r] < 0 || preint_index[r] >= n_preint || !quat_ok(pose_ij7 + 7 * r + 3)) return FGO_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FGO_ENODEV;   // no CPU fallback
-  if (hipSetDevice(device) != hipSuccess) return FGO_ENODEV;
+  if (int rc = select_device(device)) return rc;
   const size_t n = (size_t)n_records, D = sizeof(double);
-  Arena M;
-  // inputs (host pointer, bytes), then the result records, then the outputs that were asked for
-  const void *in_host[5] = {pose_ij7, info_ut21 ? info_ut21 : cov36, preint, preint_index, bias_i6};
-  const size_t in_bytes[5] = {7 * n * D, (info_ut21 ? 21 : 36) * n * D, (size_t)n_preint * sizeof(fgo_preint), n * sizeof(int64_t),
-                              bias_i6 ? 6 * n * D : 0};
-  size_t in_off[5];
-  for (int k = 0; k < 5; ++k) in_off[k] = M.reserve(in_bytes[k]);
-  const size_t res_off = M.reserve(n * sizeof(fgo_imu_check_result));
-  void *out_host[2] = {dw_out, cov_dw9_out};
-  const size_t out_bytes[2] = {3 * n * D, 9 * n * D};
-  size_t out_off[2];
-  for (int k = 0; k < 2; ++k) out_off[k] = out_host[k] ? M.reserve(out_bytes[k]) : 0;
-  if (M.alloc() != hipSuccess) return FGO_ENOMEM;
-  for (int k = 0; k < 5; ++k)
-    if (in_bytes[k] && hipMemcpy(M.at<char>(in_off[k]), in_host[k], in_bytes[k], hipMemcpyHostToDevice) != hipSuccess) return FGO_ENUM;
+  // inputs, then the result records, then the outputs that were asked for
+  Staged S;
+  const int h_pose = S.in(pose_ij7, 7 * n * D), h_info = S.in(info_ut21, 21 * n * D), h_cov = S.in(cov36, 36 * n * D);
+  const int h_preint = S.in(preint, (size_t)n_preint * sizeof(fgo_preint)), h_index = S.in(preint_index, n * sizeof(int64_t));
+  const int h_bias = S.in(bias_i6, 6 * n * D);
+  const int h_res = S.out(result, n * sizeof(fgo_imu_check_result)), h_dw = S.out(dw_out, 3 * n * D), h_cov_dw = S.out(cov_dw9_out, 9 * n * D);
+  if (int rc = S.alloc()) return rc;
+  if (int rc = S.upload()) return rc;
   IcArgs A;
   A.n = n_records;
-  A.pose = M.at<double>(in_off[0]);
-  A.info = info_ut21 ? M.at<double>(in_off[1]) : nullptr;
-  A.cov = cov36 ? M.at<double>(in_off[1]) : nullptr;
-  A.preint = M.at<fgo_preint>(in_off[2]);
-  A.index = M.at<int64_t>(in_off[3]);
-  A.bias = bias_i6 ? M.at<double>(in_off[4]) : nullptr;
+  A.pose = S.ptr<double>(h_pose); A.info = S.ptr<double>(h_info); A.cov = S.ptr<double>(h_cov);
+  A.preint = S.ptr<fgo_preint>(h_preint);
+  A.index = S.ptr<int64_t>(h_index);
+  A.bias = S.ptr<double>(h_bias);
   for (int k = 0; k < 4; ++k) A.q_uc[k] = imu_q_cam4 ? imu_q_cam4[k] : (k == 3 ? 1.0 : 0.0);
   A.d2_gate = P.d2_gate; A.d2_ref_gate = P.d2_ref_gate; A.failed00 = P.failed_info00;
-  A.res = M.at<fgo_imu_check_result>(res_off);
-  A.dw = dw_out ? M.at<double>(out_off[0]) : nullptr;
-  A.cov_dw = cov_dw9_out ? M.at<double>(out_off[1]) : nullptr;
+  A.res = S.ptr<fgo_imu_check_result>(h_res);
+  A.dw = S.ptr<double>(h_dw); A.cov_dw = S.ptr<double>(h_cov_dw);
   hipLaunchKernelGGL(k_imu_check, dim3((unsigned)n_records), dim3(64), 0, 0, A);
   if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return FGO_ENUM;
-  if (hipMemcpy(result, A.res, n * sizeof(fgo_imu_check_result), hipMemcpyDeviceToHost) != hipSuccess) return FGO_ENUM;
-  for (int k = 0; k < 2; ++k)
-    if (out_host[k] && hipMemcpy(out_host[k], M.at<char>(out_off[k]), out_bytes[k], hipMemcpyDeviceToHost) != hipSuccess) return FGO_ENUM;
-  return FGO_OK;
+  return S.download();
 }

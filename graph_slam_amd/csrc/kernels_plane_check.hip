@@ -31,6 +31,8 @@
 #include "../../include/fgo.h"
 #include "device_plan.hpp"
 #include "factors_device.hpp"
+#include "small_dense_device.hpp"
+#include "batch_call.hpp"
 
 namespace fgo {
 using namespace dev;
@@ -51,82 +53,6 @@ struct PcArgs {
   double *d2, *raw, *pred, *pred_cov, *sdj;
 };
 
-__device__ __forceinline__ constexpr int lt(int r, int c) { return r * (r + 1) / 2 + c; }           // lower triangle packed by rows
-__device__ __forceinline__ constexpr int ut(int r, int c) { return r * 6 - r * (r - 1) / 2 + c - r; }   // upper triangle of a 6x6, by rows
-
-// lower Cholesky factor (l00 l10 l11 l20 l21 l22) of the symmetric 3x3 matrix a00 a10 a11 a20 a21 a22; false if a pivot is not
-// positive (NaN included): the factor then carries a unit pivot there and nothing downstream divides by zero
-__device__ __forceinline__ bool chol3(double a00, double a10, double a11, double a20, double a21, double a22, double l[6]) {
-  const bool ok0 = a00 > 0;
-  l[0] = sqrt(ok0 ? a00 : 1.0);
-  l[1] = a10 / l[0];
-  l[3] = a20 / l[0];
-  const double s1 = a11 - l[1] * l[1];
-  const bool ok1 = s1 > 0;
-  l[2] = sqrt(ok1 ? s1 : 1.0);
-  l[4] = (a21 - l[3] * l[1]) / l[2];
-  const double s2 = a22 - l[3] * l[3] - l[4] * l[4];
-  const bool ok2 = s2 > 0;
-  l[5] = sqrt(ok2 ? s2 : 1.0);
-  return ok0 && ok1 && ok2;
-}
-// y = L^-1 e, returns y^T y = e^T (L L^T)^-1 e
-__device__ __forceinline__ double solve3_sq(const double l[6], double e0, double e1, double e2) {
-  const double y0 = e0 / l[0];
-  const double y1 = (e1 - l[1] * y0) / l[2];
-  const double y2 = (e2 - l[3] * y0 - l[4] * y1) / l[5];
-  return y0 * y0 + y1 * y1 + y2 * y2;
-}
-
-// S = A^-1 (upper triangle, by rows) of the symmetric 6x6 A given by its upper triangle; false if a pivot is <= 0 or not finite
-__device__ __forceinline__ bool inv6(const double *__restrict__ a_ut, double S[21]) {
-  double a[21];
-#pragma unroll
-  for (int r = 0; r < 6; ++r)
-#pragma unroll
-    for (int c = 0; c <= r; ++c) a[lt(r, c)] = a_ut[ut(c, r)];
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double d = a[lt(j, j)];
-#pragma unroll
-    for (int k = 0; k < j; ++k) d -= a[lt(j, k)] * a[lt(j, k)];
-    const bool okj = d > 0 && d < __builtin_huge_val();
-    ok = ok && okj;
-    const double l = sqrt(okj ? d : 1.0);
-    a[lt(j, j)] = l;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double s = a[lt(i, j)];
-#pragma unroll
-      for (int k = 0; k < j; ++k) s -= a[lt(i, k)] * a[lt(j, k)];
-      a[lt(i, j)] = s / l;
-    }
-  }
-  double Mi[21];                                   // L^-1, lower, packed by rows
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    Mi[lt(c, c)] = 1.0 / a[lt(c, c)];
-#pragma unroll
-    for (int r = c + 1; r < 6; ++r) {
-      double s = 0;
-#pragma unroll
-      for (int k = c; k < r; ++k) s += a[lt(r, k)] * Mi[lt(k, c)];
-      Mi[lt(r, c)] = -s / a[lt(r, r)];
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 6; ++r)
-#pragma unroll
-    for (int c = r; c < 6; ++c) {                  // A^-1 = L^-T L^-1
-      double s = 0;
-#pragma unroll
-      for (int k = c; k < 6; ++k) s += Mi[lt(k, r)] * Mi[lt(k, c)];
-      S[ut(r, c)] = s;
-    }
-  return ok;
-}
-
 // the 3x3 block (r0, c0) of the symmetric 6x6 held as its upper triangle
 __device__ __forceinline__ M3 block3(const double S[21], int r0, int c0) {
   M3 B;
@@ -135,7 +61,7 @@ __device__ __forceinline__ M3 block3(const double S[21], int r0, int c0) {
 #pragma unroll
     for (int b = 0; b < 3; ++b) {
       const int r = r0 + a, c = c0 + b;
-      B.m[a * 3 + b] = r <= c ? S[ut(r, c)] : S[ut(c, r)];
+      B.m[a * 3 + b] = r <= c ? S[ut6(r, c)] : S[ut6(c, r)];
     }
   return B;
 }
@@ -235,7 +161,7 @@ __global__ __launch_bounds__(64) void k_plane_check(PcArgs A) {
 #pragma unroll
     for (int r = 0; r < 6; ++r)
 #pragma unroll
-      for (int k = r; k < 6; ++k) S[ut(r, k)] = c[r * 6 + k];
+      for (int k = r; k < 6; ++k) S[ut6(r, k)] = c[r * 6 + k];
   } else {
     const double *__restrict__ a = A.info + 21 * rec;
     if (A.failed00 > 0 && a[0] == A.failed00) status = FGO_PC_SKIPPED;     // the failed-VO sentinel (:171)
@@ -375,23 +301,6 @@ __global__ __launch_bounds__(64) void k_plane_check(PcArgs A) {
   if (lane == 0) A.res[rec] = {FGO_PC_OK, n_matched, n_bad, best_i, best_j, 0, best, best_raw};
 }
 
-// Every device array of a call lives in ONE allocation: a call costs one hipMalloc / hipFree whatever it asks for.  reserve() hands
-// out offsets (256-byte aligned) before the allocation is made, at() turns them into pointers afterwards.
-struct Arena {
-  char *base = nullptr;
-  size_t total = 0;
-  ~Arena() { if (base) (void)hipFree(base); }
-  size_t reserve(size_t bytes) { const size_t o = total; total += (bytes + 255) & ~(size_t)255; return o; }
-  hipError_t alloc() { return hipMalloc((void **)&base, total ? total : 1); }
-  template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(base + off); }
-};
-// a ptr array is non-negative and non-decreasing, and no record holds more planes than an int counts
-bool ptr_ok(const int64_t *ptr, int64_t n) {
-  if (ptr[0] < 0) return false;
-  for (int64_t r = 0; r < n; ++r)
-    if (ptr[r + 1] < ptr[r] || ptr[r + 1] - ptr[r] > INT_MAX) return false;
-  return true;
-}
 bool normals_ok(const double *abcd, int64_t first, int64_t last) {
   for (int64_t k = first; k < last; ++k) {
     const double *a = abcd + 4 * k, nn = a[0] * a[0] + a[1] * a[1] + a[2] * a[2];
@@ -422,53 +331,36 @@ extern "C" int fgo_plane_check_vro_batch(int device, int64_t n_records, const do
   if (n_records < 0 || n_records > INT_MAX || !(P.cos_min >= -1 && P.cos_min <= 1) || !(P.d_max >= 0)) return FGO_EINVAL;
   if (n_records == 0) return FGO_OK;
   if (!pose_ij7 || !pi_ptr || !pj_ptr || !result || (info_ut21 != nullptr) == (cov36 != nullptr)) return FGO_EINVAL;
-  if (!ptr_ok(pi_ptr, n_records) || !ptr_ok(pj_ptr, n_records)) return FGO_EINVAL;
+  if (!csr_ptr_ok(pi_ptr, n_records, INT_MAX) || !csr_ptr_ok(pj_ptr, n_records, INT_MAX)) return FGO_EINVAL;   // an int counts a record's planes
   const int64_t Mi = pi_ptr[n_records], Mj = pj_ptr[n_records];
   if ((Mi > 0 && (!pi_abcd || !pi_cov16)) || (Mj > 0 && (!pj_abcd || !pj_cov16))) return FGO_EINVAL;
-  for (int64_t r = 0; r < n_records; ++r) {
-    const double *q = pose_ij7 + 7 * r + 3, qq = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
-    if (!(qq > 0) || !std::isfinite(qq)) return FGO_EINVAL;
-  }
+  for (int64_t r = 0; r < n_records; ++r)
+    if (!quat_ok(pose_ij7 + 7 * r + 3)) return FGO_EINVAL;
   if (!normals_ok(pi_abcd, pi_ptr[0], Mi) || !normals_ok(pj_abcd, pj_ptr[0], Mj)) return FGO_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FGO_ENODEV;   // no CPU fallback
-  if (hipSetDevice(device) != hipSuccess) return FGO_ENODEV;
+  if (int rc = select_device(device)) return rc;
   const size_t n = (size_t)n_records, mi = (size_t)Mi, mj = (size_t)Mj, D = sizeof(double);
-  Arena M;
-  // inputs (host pointer, bytes), then the result records, then the per-plane outputs that were asked for
-  const void *in_host[8] = {pose_ij7, info_ut21 ? info_ut21 : cov36, pi_ptr, pj_ptr, pi_abcd, pi_cov16, pj_abcd, pj_cov16};
-  const size_t in_bytes[8] = {7 * n * D, (info_ut21 ? 21 : 36) * n * D, (n + 1) * sizeof(int64_t), (n + 1) * sizeof(int64_t),
-                              4 * mi * D, 16 * mi * D, 4 * mj * D, 16 * mj * D};
-  size_t in_off[8];
-  for (int k = 0; k < 8; ++k) in_off[k] = M.reserve(in_bytes[k]);
-  const size_t res_off = M.reserve(n * sizeof(fgo_plane_check_result));
-  void *out_host[6] = {match_out, d2_out, raw_out, pred_abcd_out, pred_cov9_out, sdj_out};
-  const size_t out_bytes[6] = {mi * sizeof(int64_t), mi * D, mi * D, 4 * mi * D, 9 * mi * D, mi * D};
-  size_t out_off[6];
-  for (int k = 0; k < 6; ++k) out_off[k] = out_host[k] ? M.reserve(out_bytes[k]) : 0;
-  if (M.alloc() != hipSuccess) return FGO_ENOMEM;
-  for (int k = 0; k < 8; ++k)
-    if (in_bytes[k] && hipMemcpy(M.at<char>(in_off[k]), in_host[k], in_bytes[k], hipMemcpyHostToDevice) != hipSuccess) return FGO_ENUM;
+  // inputs, then the result records, then the per-plane outputs that were asked for
+  Staged S;
+  const int h_pose = S.in(pose_ij7, 7 * n * D), h_info = S.in(info_ut21, 21 * n * D), h_cov = S.in(cov36, 36 * n * D);
+  const int h_pi_ptr = S.in(pi_ptr, (n + 1) * sizeof(int64_t)), h_pj_ptr = S.in(pj_ptr, (n + 1) * sizeof(int64_t));
+  const int h_pi_abcd = S.in(pi_abcd, 4 * mi * D), h_pi_cov = S.in(pi_cov16, 16 * mi * D);
+  const int h_pj_abcd = S.in(pj_abcd, 4 * mj * D), h_pj_cov = S.in(pj_cov16, 16 * mj * D);
+  const int h_res = S.out(result, n * sizeof(fgo_plane_check_result));
+  const int h_match = S.out(match_out, mi * sizeof(int64_t)), h_d2 = S.out(d2_out, mi * D), h_raw = S.out(raw_out, mi * D);
+  const int h_pred = S.out(pred_abcd_out, 4 * mi * D), h_pred_cov = S.out(pred_cov9_out, 9 * mi * D), h_sdj = S.out(sdj_out, mi * D);
+  if (int rc = S.alloc()) return rc;
+  if (int rc = S.upload()) return rc;
   PcArgs A;
   A.n = n_records;
-  A.pose = M.at<double>(in_off[0]);
-  A.info = info_ut21 ? M.at<double>(in_off[1]) : nullptr;
-  A.cov = cov36 ? M.at<double>(in_off[1]) : nullptr;
-  A.pi_ptr = M.at<int64_t>(in_off[2]); A.pj_ptr = M.at<int64_t>(in_off[3]);
-  A.pi_abcd = M.at<double>(in_off[4]); A.pi_cov = M.at<double>(in_off[5]);
-  A.pj_abcd = M.at<double>(in_off[6]); A.pj_cov = M.at<double>(in_off[7]);
+  A.pose = S.ptr<double>(h_pose); A.info = S.ptr<double>(h_info); A.cov = S.ptr<double>(h_cov);
+  A.pi_ptr = S.ptr<int64_t>(h_pi_ptr); A.pj_ptr = S.ptr<int64_t>(h_pj_ptr);
+  A.pi_abcd = S.ptr<double>(h_pi_abcd); A.pi_cov = S.ptr<double>(h_pi_cov);
+  A.pj_abcd = S.ptr<double>(h_pj_abcd); A.pj_cov = S.ptr<double>(h_pj_cov);
   A.cos_min = P.cos_min; A.d_max = P.d_max; A.failed00 = P.failed_info00;
-  A.res = M.at<fgo_plane_check_result>(res_off);
-  A.match = match_out ? M.at<int64_t>(out_off[0]) : nullptr;
-  A.d2 = d2_out ? M.at<double>(out_off[1]) : nullptr;
-  A.raw = raw_out ? M.at<double>(out_off[2]) : nullptr;
-  A.pred = pred_abcd_out ? M.at<double>(out_off[3]) : nullptr;
-  A.pred_cov = pred_cov9_out ? M.at<double>(out_off[4]) : nullptr;
-  A.sdj = sdj_out ? M.at<double>(out_off[5]) : nullptr;
+  A.res = S.ptr<fgo_plane_check_result>(h_res);
+  A.match = S.ptr<int64_t>(h_match); A.d2 = S.ptr<double>(h_d2); A.raw = S.ptr<double>(h_raw);
+  A.pred = S.ptr<double>(h_pred); A.pred_cov = S.ptr<double>(h_pred_cov); A.sdj = S.ptr<double>(h_sdj);
   hipLaunchKernelGGL(k_plane_check, dim3((unsigned)n_records), dim3(64), 0, 0, A);
   if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return FGO_ENUM;
-  if (hipMemcpy(result, A.res, n * sizeof(fgo_plane_check_result), hipMemcpyDeviceToHost) != hipSuccess) return FGO_ENUM;
-  for (int k = 0; k < 6; ++k)
-    if (out_host[k] && out_bytes[k] && hipMemcpy(out_host[k], M.at<char>(out_off[k]), out_bytes[k], hipMemcpyDeviceToHost) != hipSuccess) return FGO_ENUM;
-  return FGO_OK;
+  return S.download();
 }

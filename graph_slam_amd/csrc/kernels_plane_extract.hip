@@ -29,8 +29,12 @@
 #include <climits>
 #include <cmath>
 #include "../../include/fgo.h"
+#include "small_dense_device.hpp"
+#include "batch_call.hpp"
 
 namespace fgo {
+using namespace dev;
+
 namespace {
 
 constexpr int PX_WAVES = 4;                      // waves of a workgroup
@@ -60,60 +64,6 @@ struct PxArgs {
   fgo_plane_extract_result *res;
 };
 
-__device__ __forceinline__ double wsum(double v) {     // every lane ends with the same bits (each step adds the same two numbers on both sides)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int wsum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// larger count first, then the lower hypothesis
-__device__ __forceinline__ void better(int &cnt, int &h, int cnt2, int h2) {
-  if (cnt2 > cnt || (cnt2 == cnt && h2 < h)) { cnt = cnt2; h = h2; }
-}
-
-// the sums of a workgroup: butterfly inside a wave, the waves in wave order; two barriers, the first lets the readers of the
-// previous sum finish.  Every thread of the workgroup has to call it.
-template <class T, int N>
-__device__ __forceinline__ void bsum(T (&v)[N], T *red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int c = 0; c < N; ++c) v[c] = wsum(v[c]);
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int c = 0; c < N; ++c) red[wave * N + c] = v[c];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int c = 0; c < N; ++c) {
-    T t = red[c];
-#pragma unroll
-    for (int w = 1; w < PX_WAVES; ++w) t += red[w * N + c];
-    v[c] = t;
-  }
-}
-
-__device__ __forceinline__ uint64_t mix(uint64_t z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-// the VRO sampler with the round folded into the counter: hc = r K + h
-__device__ __forceinline__ void sample3(uint64_t seed, uint64_t hc, int M, int &a, int &b, int &c) {
-  const uint64_t g = 0x9E3779B97F4A7C15ull, k0 = 3ull * hc + 1ull;
-  a = (int)(mix(seed + k0 * g) % (uint64_t)M);
-  b = (int)(mix(seed + (k0 + 1) * g) % (uint64_t)(M - 1));
-  b += b >= a;
-  c = (int)(mix(seed + (k0 + 2) * g) % (uint64_t)(M - 2));
-  c += c >= min(a, b);
-  c += c >= max(a, b);
-}
-
 struct Pl { double n[3], d; };
 
 // |n.p + d| with the roundings spelled out: the scoring, the refinement and the final pass have to agree on every point
@@ -141,34 +91,6 @@ __device__ __forceinline__ bool hypothesis(const PxArgs &A, const double *__rest
   return true;
 }
 
-// one cyclic Jacobi rotation on the symmetric 3x3 a (full storage) with the eigenvectors accumulated in the columns of v
-template <int P, int Q>
-__device__ __forceinline__ void jacobi_rot(double a[9], double v[9]) {
-  const double apq = a[3 * P + Q];
-  if (apq == 0.0) return;
-  const double theta = (a[3 * Q + Q] - a[3 * P + P]) / (2.0 * apq);
-  const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-  const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {                    // columns P, Q
-    const double akp = a[3 * k + P], akq = a[3 * k + Q];
-    a[3 * k + P] = c * akp - s * akq;
-    a[3 * k + Q] = s * akp + c * akq;
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {                    // rows P, Q
-    const double apk = a[3 * P + k], aqk = a[3 * Q + k];
-    a[3 * P + k] = c * apk - s * aqk;
-    a[3 * Q + k] = s * apk + c * aqk;
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double vkp = v[3 * k + P], vkq = v[3 * k + Q];
-    v[3 * k + P] = c * vkp - s * vkq;
-    v[3 * k + Q] = s * vkp + c * vkq;
-  }
-}
-
 // The total-least-squares plane of the points sel names among `count` slots (sel(i) = the pixel of slot i, or -1), by every thread
 // of the workgroup: the centroid, the scatter of the centred points (two passes), the eigenvector of the smallest eigenvalue.
 // N = the number of points.  N == 0 leaves non-finite values behind; the callers never fit an empty set.
@@ -181,7 +103,7 @@ __device__ __forceinline__ void fit_plane(const double *__restrict__ pts, int co
     const double *p = pts + 3 * (int64_t)pix;
     s[0] += p[0]; s[1] += p[1]; s[2] += p[2]; s[3] += 1.0;
   }
-  bsum(s, red);
+  bsum<PX_WAVES>(s, red);
   N = (int)s[3];                                  // exact: at most 2^24 ones
 #pragma unroll
   for (int k = 0; k < 3; ++k) cen[k] = s[k] / s[3];
@@ -193,12 +115,12 @@ __device__ __forceinline__ void fit_plane(const double *__restrict__ pts, int co
     const double x = p[0] - cen[0], y = p[1] - cen[1], z = p[2] - cen[2];
     q[0] += x * x; q[1] += x * y; q[2] += x * z; q[3] += y * y; q[4] += y * z; q[5] += z * z;
   }
-  bsum(q, red);
+  bsum<PX_WAVES>(q, red);
   double a[9] = {q[0], q[1], q[2], q[1], q[3], q[4], q[2], q[4], q[5]};
   double v[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
 #pragma unroll 1
   for (int sweep = 0; sweep < PX_SWEEPS; ++sweep) {
-    jacobi_rot<0, 1>(a, v); jacobi_rot<0, 2>(a, v); jacobi_rot<1, 2>(a, v);
+    jacobi_rot<3, 0, 1>(a, v); jacobi_rot<3, 0, 2>(a, v); jacobi_rot<3, 1, 2>(a, v);
   }
   double least = a[0], e[3] = {v[0], v[3], v[6]};
 #pragma unroll
@@ -210,7 +132,6 @@ __device__ __forceinline__ void fit_plane(const double *__restrict__ pts, int co
   orient(P);
 }
 
-__device__ __forceinline__ bool pivot_ok(double d) { return d > 0 && d < __builtin_huge_val(); }
 __device__ __forceinline__ bool finite(double d) { return fabs(d) < __builtin_huge_val(); }
 
 __global__ __launch_bounds__(PX_T) void k_plane_extract(PxArgs A) {
@@ -245,7 +166,7 @@ __global__ __launch_bounds__(PX_T) void k_plane_extract(PxArgs A) {
     lab[pix] = valid ? -1 : -2;
     nv[0] += valid;
   }
-  bsum(nv, red_i);                                 // its barriers publish pts and lab to the workgroup
+  bsum<PX_WAVES>(nv, red_i);                                 // its barriers publish pts and lab to the workgroup
   const int n_valid_pixels = nv[0];
 
   // ---- rounds: everything below that is not indexed by a pixel is uniform over the workgroup
@@ -326,7 +247,7 @@ __global__ __launch_bounds__(PX_T) void k_plane_extract(PxArgs A) {
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) better(my_cnt, my_h, __shfl_xor(my_cnt, o, 64), __shfl_xor(my_h, o, 64));
-    my_valid = wsum(my_valid);
+    my_valid = wave_sum(my_valid);
     __syncthreads();                               // the readers of the round before are done
     if (lane == 0) { w_cnt[wave] = my_cnt; w_h[wave] = my_h; w_valid[wave] = my_valid; }
     __syncthreads();
@@ -357,7 +278,7 @@ __global__ __launch_bounds__(PX_T) void k_plane_extract(PxArgs A) {
         chg[1] += in;
         inset[i] = in;
       }
-      bsum(chg, red_i);
+      bsum<PX_WAVES>(chg, red_i);
       if (chg[1] < A.min_pixels) { keep = false; break; }
       if (chg[0] == 0) break;
     }
@@ -391,7 +312,7 @@ __global__ __launch_bounds__(PX_T) void k_plane_extract(PxArgs A) {
 #pragma unroll
     for (int k = 0; k < FGO_PX_MAX_PLANES; ++k) cntk[k] += best == k;
   }
-  bsum(cntk, red_i);
+  bsum<PX_WAVES>(cntk, red_i);
   int n_planes = 0;
 #pragma unroll
   for (int k = 0; k < FGO_PX_MAX_PLANES; ++k) {
@@ -446,7 +367,7 @@ __global__ __launch_bounds__(PX_T) void k_plane_extract(PxArgs A) {
       s[1] += j0 * j0; s[2] += j0 * j1; s[3] += j0; s[4] += j1 * j1; s[5] += j1; s[6] += 1.0;
       s[7] += v * j0 * j0; s[8] += v * j0 * j1; s[9] += v * j0; s[10] += v * j1 * j1; s[11] += v * j1; s[12] += v;
     }
-    bsum(s, red_d);
+    bsum<PX_WAVES>(s, red_d);
     const double rmse = sqrt(s[0] / (double)N);
     // A = L L^T, Ai = A^-1 = L^-T L^-1
     const bool ok0 = pivot_ok(s[1]);
@@ -520,21 +441,6 @@ __global__ __launch_bounds__(PX_T) void k_plane_extract(PxArgs A) {
   if (tid == 0) A.res[frame] = {status, n_planes, n_valid_pixels, rounds_run};
 }
 
-// Every device array of a call lives in ONE allocation: a call costs one hipMalloc / hipFree whatever it asks for.  reserve() hands
-// out offsets (256-byte aligned) before the allocation is made, at() turns them into pointers afterwards.
-struct Arena {
-  char *base = nullptr;
-  size_t total = 0;
-  ~Arena() { if (base) (void)hipFree(base); }
-  size_t reserve(size_t bytes) { const size_t o = total; total += (bytes + 255) & ~(size_t)255; return o; }
-  hipError_t alloc() { return hipMalloc((void **)&base, total ? total : 1); }
-  template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(base + off); }
-};
-struct Events {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
 double g_kernel_ms = 0.0;
 
 }  // namespace
@@ -577,38 +483,36 @@ extern "C" int fgo_plane_extract_batch(int device, int64_t n_frames, int width, 
   if (!(P.sigma_z[0] >= 0) || !(P.sigma_z[1] >= 0) || !(P.sigma_z[2] >= 0) || !(P.sigma_z[0] + P.sigma_z[1] + P.sigma_z[2] > 0)) return FGO_EINVAL;
   if (n_frames == 0) return FGO_OK;
   if (!depth || !result || !abcd_out || !cov16_out) return FGO_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FGO_ENODEV;   // no CPU fallback
-  if (hipSetDevice(device) != hipSuccess) return FGO_ENODEV;
+  if (int rc = select_device(device)) return rc;
   const size_t n = (size_t)n_frames, np = (size_t)width * (size_t)height, D = sizeof(double), K = (size_t)P.hypotheses, mp = (size_t)P.max_planes;
-  Arena M;
-  const size_t in_off = M.reserve(n * np * sizeof(uint16_t));
-  // scratch: the points, the candidates and the set; then the outputs (the labels are always there: the kernel works in them)
-  const size_t pts_off = M.reserve(3 * n * np * D), cand_off = M.reserve(n * np * sizeof(int32_t)), set_off = M.reserve(n * np);
-  void *out_host[7] = {result, abcd_out, cov16_out, cov_ut6_out, plane_out, label_out, hyp_count_out};
-  const size_t out_bytes[7] = {n * sizeof(fgo_plane_extract_result), 4 * n * mp * D, 16 * n * mp * D, 6 * n * mp * D,
-                               n * mp * sizeof(fgo_plane_extract_plane), n * np, n * mp * K * sizeof(int32_t)};
-  size_t out_off[7];
-  for (int k = 0; k < 7; ++k) out_off[k] = (out_host[k] || k == 5) ? M.reserve(out_bytes[k]) : 0;
-  if (M.alloc() != hipSuccess) return FGO_ENOMEM;
-  if (hipMemcpy(M.at<char>(in_off), depth, n * np * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess) return FGO_ENUM;
-  for (int k = 1; k <= 4; ++k)                                  // the slots past a frame's last plane stay zero
-    if (out_host[k] && hipMemset(M.at<char>(out_off[k]), 0, out_bytes[k]) != hipSuccess) return FGO_ENUM;
+  // the input; scratch: the points, the candidates and the set; then the outputs (the labels are always there: the kernel works in them)
+  Staged S;
+  const int h_depth = S.in(depth, n * np * sizeof(uint16_t));
+  const int h_pts = S.out(nullptr, 3 * n * np * D, true), h_cand = S.out(nullptr, n * np * sizeof(int32_t), true), h_set = S.out(nullptr, n * np, true);
+  const int h_res = S.out(result, n * sizeof(fgo_plane_extract_result));
+  void *const slot_host[4] = {abcd_out, cov16_out, cov_ut6_out, plane_out};
+  const size_t slot_bytes[4] = {4 * n * mp * D, 16 * n * mp * D, 6 * n * mp * D, n * mp * sizeof(fgo_plane_extract_plane)};
+  int h_slot[4];
+  for (int k = 0; k < 4; ++k) h_slot[k] = S.out(slot_host[k], slot_bytes[k]);
+  const int h_label = S.out(label_out, n * np, true), h_hyp = S.out(hyp_count_out, n * mp * K * sizeof(int32_t));
+  if (int rc = S.alloc()) return rc;
+  if (int rc = S.upload()) return rc;
+  for (int k = 0; k < 4; ++k)                                   // the slots past a frame's last plane stay zero
+    if (slot_host[k] && hipMemset(S.ptr<char>(h_slot[k]), 0, slot_bytes[k]) != hipSuccess) return FGO_ENUM;
   PxArgs A;
   A.n = n_frames; A.W = width; A.NP = (int)np;
-  A.depth = M.at<uint16_t>(in_off);
+  A.depth = S.ptr<uint16_t>(h_depth);
   A.fx = P.fx; A.fy = P.fy; A.cx = P.cx; A.cy = P.cy; A.z_scale = P.z_scale; A.z_min = P.z_min; A.z_max = P.z_max;
   A.max_dist = P.max_dist; A.min_area = P.min_area; A.s_px2 = P.sigma_px * P.sigma_px;
   A.sz0 = P.sigma_z[0]; A.sz1 = P.sigma_z[1]; A.sz2 = P.sigma_z[2];
   A.K = P.hypotheses; A.min_pixels = P.min_pixels; A.max_planes = P.max_planes; A.refine_rounds = P.refine_rounds;
   A.seed = P.seed;
-  A.pts = M.at<double>(pts_off); A.cand = M.at<int32_t>(cand_off); A.inset = M.at<uint8_t>(set_off);
-  A.res = M.at<fgo_plane_extract_result>(out_off[0]);
-  A.abcd = M.at<double>(out_off[1]); A.cov16 = M.at<double>(out_off[2]);
-  A.ut6 = cov_ut6_out ? M.at<double>(out_off[3]) : nullptr;
-  A.plane = plane_out ? M.at<fgo_plane_extract_plane>(out_off[4]) : nullptr;
-  A.label = M.at<int8_t>(out_off[5]);
-  A.hyp = hyp_count_out ? M.at<int32_t>(out_off[6]) : nullptr;
+  A.pts = S.ptr<double>(h_pts); A.cand = S.ptr<int32_t>(h_cand); A.inset = S.ptr<uint8_t>(h_set);
+  A.res = S.ptr<fgo_plane_extract_result>(h_res);
+  A.abcd = S.ptr<double>(h_slot[0]); A.cov16 = S.ptr<double>(h_slot[1]); A.ut6 = S.ptr<double>(h_slot[2]);
+  A.plane = S.ptr<fgo_plane_extract_plane>(h_slot[3]);
+  A.label = S.ptr<int8_t>(h_label);
+  A.hyp = S.ptr<int32_t>(h_hyp);
   Events ev;
   if (hipEventCreate(&ev.a) != hipSuccess || hipEventCreate(&ev.b) != hipSuccess) return FGO_ENUM;
   (void)hipEventRecord(ev.a, 0);
@@ -617,8 +521,5 @@ extern "C" int fgo_plane_extract_batch(int device, int64_t n_frames, int width, 
   if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return FGO_ENUM;
   float ms = 0;
   g_kernel_ms = hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess ? (double)ms : 0.0;
-  for (int k = 0; k < 7; ++k)
-    if (out_host[k] && out_bytes[k] && hipMemcpy(out_host[k], M.at<char>(out_off[k]), out_bytes[k], hipMemcpyDeviceToHost) != hipSuccess)
-      return FGO_ENUM;
-  return FGO_OK;
+  return S.download();
 }

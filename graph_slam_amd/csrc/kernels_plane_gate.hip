@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include "device_plan.hpp"
 #include "factors_device.hpp"
+#include "small_dense_device.hpp"
 
 namespace fgo {
 using namespace dev;
@@ -27,30 +28,6 @@ namespace {
 
 constexpr int PG_G = 21;                       // lane groups of 3 in the one-wave workgroup
 constexpr int PG_LDS = 39;                     // doubles per group: Jx (18), Jp (9), M = P + S (9), e (3)
-
-// lower Cholesky factor (l00 l10 l11 l20 l21 l22) of the symmetric 3x3 matrix a00 a10 a11 a20 a21 a22; false if a pivot is not
-// positive (NaN included): the factor then carries a unit pivot there and nothing downstream divides by zero
-__device__ __forceinline__ bool chol3(double a00, double a10, double a11, double a20, double a21, double a22, double l[6]) {
-  const bool ok0 = a00 > 0;
-  l[0] = sqrt(ok0 ? a00 : 1.0);
-  l[1] = a10 / l[0];
-  l[3] = a20 / l[0];
-  const double s1 = a11 - l[1] * l[1];
-  const bool ok1 = s1 > 0;
-  l[2] = sqrt(ok1 ? s1 : 1.0);
-  l[4] = (a21 - l[3] * l[1]) / l[2];
-  const double s2 = a22 - l[3] * l[3] - l[4] * l[4];
-  const bool ok2 = s2 > 0;
-  l[5] = sqrt(ok2 ? s2 : 1.0);
-  return ok0 && ok1 && ok2;
-}
-// y = L^-1 e, returns y^T y = e^T (L L^T)^-1 e
-__device__ __forceinline__ double solve3_sq(const double l[6], double e0, double e1, double e2) {
-  const double y0 = e0 / l[0];
-  const double y1 = (e1 - l[1] * y0) / l[2];
-  const double y2 = (e2 - l[3] * y0 - l[4] * y1) / l[5];
-  return y0 * y0 + y1 * y1 + y2 * y2;
-}
 
 __global__ __launch_bounds__(64) void k_plane_gate(PlaneGatePlan A, const double *__restrict__ vals) {
   __shared__ double lds[PG_G * PG_LDS];

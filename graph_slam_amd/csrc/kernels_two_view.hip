@@ -28,6 +28,8 @@
 #include "../../include/fgo.h"
 #include "device_plan.hpp"
 #include "factors_device.hpp"
+#include "small_dense_device.hpp"
+#include "batch_call.hpp"
 
 namespace fgo {
 using namespace dev;
@@ -45,12 +47,6 @@ struct TvConst {
   double w_pose, w_pt, s_pix;   // 1 / sigma^2 of the pose and point priors, 1 / sigma of a pixel
   int max_iters, min_matches;
 };
-
-__device__ __forceinline__ double wsum_tv(double v) {     // every lane ends with the same bits (each step adds the same two numbers on both sides)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // one match, whitened: the two projection factors and the point prior
 struct PtLin {
@@ -230,7 +226,7 @@ __device__ __forceinline__ void tv_reduce(const TvConst *Cg, const Pose &Xi, con
     }
   }
   __syncthreads();
-  chi_out = wsum_tv(chi);
+  chi_out = wave_sum(chi);
   fail_out = __ballot(bad) != 0;
 }
 
@@ -270,12 +266,11 @@ __device__ __forceinline__ void tv_trial(const TvConst *Cg, const Pose &Xi, cons
     const double q0 = pc.x - mu.x, q1 = pc.y - mu.y, q2 = pc.z - mu.z;
     chi += C.w_pt * (q0 * q0 + q1 * q1 + q2 * q2);
   }
-  chi_out = wsum_tv(chi);
-  scale_out = wsum_tv(sc);
+  chi_out = wave_sum(chi);
+  scale_out = wave_sum(sc);
 }
 
-// lower-triangular 12x12 packed by rows
-__device__ __forceinline__ constexpr int lt(int r, int c) { return r * (r + 1) / 2 + c; }
+// in place: the lower Cholesky factor of the symmetric 12x12 whose lower triangle a holds, packed by rows (lt)
 __device__ __forceinline__ bool chol12(double a[78]) {
   bool ok = true;
 #pragma unroll
@@ -373,7 +368,8 @@ __global__ __launch_bounds__(64) void k_two_view(int64_t n_pairs, const int64_t 
       if (finishing) {
         R.status = (failed || !isfinite(currentError)) ? FGO_TV_NUM : FGO_TV_OK;
         if (R.status == FGO_TV_OK) {
-          // L_jj = rows / columns 6 .. 11 of the factor: information = L_jj L_jj^T, covariance = L_jj^-T L_jj^-1
+          // L_jj = rows / columns 6 .. 11 of the factor: information = L_jj L_jj^T, covariance = L_jj^-T L_jj^-1 (the last two
+          // steps of dev::inv6, kept here: see small_dense_device.hpp)
           double Mi[21];                              // L_jj^-1, lower, packed by rows
 #pragma unroll
           for (int c = 0; c < 6; ++c) {
@@ -477,18 +473,6 @@ __global__ __launch_bounds__(64) void k_two_view(int64_t n_pairs, const int64_t 
   }
 }
 
-template <class T>
-struct Dev {
-  T *p = nullptr;
-  ~Dev() { if (p) (void)hipFree(p); }
-  hipError_t put(const T *h, size_t n) {
-    hipError_t e = hipMalloc((void **)&p, sizeof(T) * (n ? n : 1));
-    if (e != hipSuccess || !n || !h) return e;
-    return hipMemcpy(p, h, sizeof(T) * n, hipMemcpyHostToDevice);
-  }
-  hipError_t get(T *h, size_t n) const { return n ? hipMemcpy(h, p, sizeof(T) * n, hipMemcpyDeviceToHost) : hipSuccess; }
-};
-
 }  // namespace
 }  // namespace fgo
 
@@ -511,9 +495,7 @@ extern "C" int fgo_two_view_ba_batch(int device, int64_t n_pairs, const int64_t 
   if (params) P = *params;
   if (n_pairs < 0 || n_pairs > INT_MAX || !(P.pose_prior_sigma > 0) || !(P.point_sigma > 0) || !(P.pixel_sigma > 0) || P.min_matches < 3) return FGO_EINVAL;
   if (n_pairs == 0) return FGO_OK;
-  if (!match_ptr || !calib9 || !pose_j_out || !result || match_ptr[0] < 0) return FGO_EINVAL;
-  for (int64_t p = 0; p < n_pairs; ++p)
-    if (match_ptr[p + 1] < match_ptr[p] || match_ptr[p + 1] - match_ptr[p] > TV_MAX_MATCHES) return FGO_EINVAL;
+  if (!match_ptr || !calib9 || !pose_j_out || !result || !csr_ptr_ok(match_ptr, n_pairs, TV_MAX_MATCHES)) return FGO_EINVAL;
   const int64_t M = match_ptr[n_pairs];
   if (M > 0 && (!xyz_i || !uv_i || !uv_j)) return FGO_EINVAL;
   TvConst C;
@@ -523,28 +505,20 @@ extern "C" int fgo_two_view_ba_batch(int device, int64_t n_pairs, const int64_t 
   C.s_pix = 1.0 / P.pixel_sigma;
   C.max_iters = P.max_iters <= 0 ? 100 : P.max_iters;
   C.min_matches = P.min_matches;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FGO_ENODEV;   // no CPU fallback
-  if (hipSetDevice(device) != hipSuccess) return FGO_ENODEV;
-  const size_t n = (size_t)n_pairs, m = (size_t)M;
-  Dev<int64_t> d_ptr;
-  Dev<double> d_xyz, d_uvi, d_uvj, d_p0, d_work, d_pj, d_pi, d_cov, d_info;
-  Dev<fgo_two_view_result> d_res;
-  Dev<TvConst> d_const;
-  if (d_ptr.put(match_ptr, n + 1) != hipSuccess || d_xyz.put(xyz_i, 3 * m) != hipSuccess || d_uvi.put(uv_i, 2 * m) != hipSuccess ||
-      d_uvj.put(uv_j, 2 * m) != hipSuccess || d_work.put(nullptr, 6 * m) != hipSuccess || d_pj.put(nullptr, 7 * n) != hipSuccess ||
-      d_res.put(nullptr, n) != hipSuccess || d_const.put(&C, 1) != hipSuccess)
-    return FGO_ENOMEM;
-  if (pose_j0 && d_p0.put(pose_j0, 7 * n) != hipSuccess) return FGO_ENOMEM;
-  if (pose_i_out && d_pi.put(nullptr, 7 * n) != hipSuccess) return FGO_ENOMEM;
-  if (cov36_out && d_cov.put(nullptr, 36 * n) != hipSuccess) return FGO_ENOMEM;
-  if (info_ut21_out && d_info.put(nullptr, 21 * n) != hipSuccess) return FGO_ENOMEM;
-  hipLaunchKernelGGL(k_two_view, dim3((unsigned)n_pairs), dim3(64), 0, 0, n_pairs, d_ptr.p, d_xyz.p, d_uvi.p, d_uvj.p, pose_j0 ? d_p0.p : nullptr, d_const.p,
-                     d_work.p, M, d_pj.p, pose_i_out ? d_pi.p : nullptr, cov36_out ? d_cov.p : nullptr, info_ut21_out ? d_info.p : nullptr, d_res.p);
+  if (int rc = select_device(device)) return rc;
+  const size_t n = (size_t)n_pairs, m = (size_t)M, D = sizeof(double);
+  // inputs, the work buffer (the current and the candidate points), then the outputs
+  Staged S;
+  const int h_ptr = S.in(match_ptr, (n + 1) * sizeof(int64_t)), h_xyz = S.in(xyz_i, 3 * m * D), h_uvi = S.in(uv_i, 2 * m * D), h_uvj = S.in(uv_j, 2 * m * D);
+  const int h_p0 = S.in(pose_j0, 7 * n * D), h_const = S.in(&C, sizeof(TvConst));
+  const int h_work = S.out(nullptr, 6 * m * D, true);
+  const int h_pj = S.out(pose_j_out, 7 * n * D), h_pi = S.out(pose_i_out, 7 * n * D), h_cov = S.out(cov36_out, 36 * n * D), h_info = S.out(info_ut21_out, 21 * n * D);
+  const int h_res = S.out(result, n * sizeof(fgo_two_view_result));
+  if (int rc = S.alloc()) return rc;
+  if (int rc = S.upload()) return rc;
+  hipLaunchKernelGGL(k_two_view, dim3((unsigned)n_pairs), dim3(64), 0, 0, n_pairs, S.ptr<int64_t>(h_ptr), S.ptr<double>(h_xyz), S.ptr<double>(h_uvi),
+                     S.ptr<double>(h_uvj), S.ptr<double>(h_p0), S.ptr<TvConst>(h_const), S.ptr<double>(h_work), M, S.ptr<double>(h_pj), S.ptr<double>(h_pi),
+                     S.ptr<double>(h_cov), S.ptr<double>(h_info), S.ptr<fgo_two_view_result>(h_res));
   if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return FGO_ENUM;
-  if (d_pj.get(pose_j_out, 7 * n) != hipSuccess || d_res.get(result, n) != hipSuccess) return FGO_ENUM;
-  if (pose_i_out && d_pi.get(pose_i_out, 7 * n) != hipSuccess) return FGO_ENUM;
-  if (cov36_out && d_cov.get(cov36_out, 36 * n) != hipSuccess) return FGO_ENUM;
-  if (info_ut21_out && d_info.get(info_ut21_out, 21 * n) != hipSuccess) return FGO_ENUM;
-  return FGO_OK;
+  return S.download();
 }

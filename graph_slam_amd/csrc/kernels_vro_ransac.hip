@@ -24,8 +24,12 @@
 #include <climits>
 #include <cmath>
 #include "../../include/fgo.h"
+#include "small_dense_device.hpp"
+#include "batch_call.hpp"
 
 namespace fgo {
+using namespace dev;
+
 namespace {
 
 constexpr int VR_CHUNK = 128;                 // matches staged in LDS at a time (6 KB)
@@ -48,37 +52,6 @@ struct VrArgs {
 };
 
 struct Rt { double R[9], t[3]; };
-
-__device__ __forceinline__ double wsum(double v) {     // every lane ends with the same bits (each step adds the same two numbers on both sides)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int wsum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// larger count first, then the lower hypothesis
-__device__ __forceinline__ void better(int &cnt, int &h, int cnt2, int h2) {
-  if (cnt2 > cnt || (cnt2 == cnt && h2 < h)) { cnt = cnt2; h = h2; }
-}
-
-__device__ __forceinline__ uint64_t mix(uint64_t z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-__device__ __forceinline__ void sample3(uint64_t seed, int h, int M, int &a, int &b, int &c) {
-  const uint64_t g = 0x9E3779B97F4A7C15ull, k0 = 3ull * (uint64_t)h + 1ull;
-  a = (int)(mix(seed + k0 * g) % (uint64_t)M);
-  b = (int)(mix(seed + (k0 + 1) * g) % (uint64_t)(M - 1));
-  b += b >= a;
-  c = (int)(mix(seed + (k0 + 2) * g) % (uint64_t)(M - 2));
-  c += c >= min(a, b);
-  c += c >= max(a, b);
-}
 
 __device__ __forceinline__ double norm3(const double v[3]) { return sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
 __device__ __forceinline__ void cross3(const double a[3], const double b[3], double c[3]) {
@@ -108,7 +81,7 @@ __device__ __forceinline__ void triad(const double *__restrict__ pa, const doubl
 // hypothesis h of a pair with M >= 3 matches at xi / xj; false if it is invalid
 __device__ __forceinline__ bool hypothesis(const VrArgs &A, const double *__restrict__ xi, const double *__restrict__ xj, int h, int M, Rt &T) {
   int a, b, c;
-  sample3(A.seed, h, M, a, b, c);
+  sample3(A.seed, (uint64_t)h, M, a, b, c);
   double Fi[9], Fj[9], abi, aci, bci, ari, abj, acj, bcj, arj;
   triad(xi + 3 * a, xi + 3 * b, xi + 3 * c, Fi, abi, aci, bci, ari);
   triad(xj + 3 * a, xj + 3 * b, xj + 3 * c, Fj, abj, acj, bcj, arj);
@@ -137,34 +110,6 @@ __device__ __forceinline__ double resid2(const Rt &T, double ix, double iy, doub
   return fma(rx, rx, fma(ry, ry, rz * rz));
 }
 
-// one cyclic Jacobi rotation on the symmetric 4x4 a (full storage) with the eigenvectors accumulated in the columns of v
-template <int P, int Q>
-__device__ __forceinline__ void jacobi_rot(double a[16], double v[16]) {
-  const double apq = a[4 * P + Q];
-  if (apq == 0.0) return;
-  const double theta = (a[4 * Q + Q] - a[4 * P + P]) / (2.0 * apq);
-  const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-  const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {                    // columns P, Q
-    const double akp = a[4 * k + P], akq = a[4 * k + Q];
-    a[4 * k + P] = c * akp - s * akq;
-    a[4 * k + Q] = s * akp + c * akq;
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {                    // rows P, Q
-    const double apk = a[4 * P + k], aqk = a[4 * Q + k];
-    a[4 * P + k] = c * apk - s * aqk;
-    a[4 * Q + k] = s * apk + c * aqk;
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double vkp = v[4 * k + P], vkq = v[4 * k + Q];
-    v[4 * k + P] = c * vkp - s * vkq;
-    v[4 * k + Q] = s * vkp + c * vkq;
-  }
-}
-
 // the rotation maximising tr(R^T C), C = sum a b^T (a: centred p_i, b: centred p_j), as a quaternion x y z w with w >= 0: the
 // eigenvector of the largest eigenvalue of Horn's N
 __device__ __forceinline__ void horn(const double C[9], double q[4]) {
@@ -177,8 +122,8 @@ __device__ __forceinline__ void horn(const double C[9], double q[4]) {
   double v[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 #pragma unroll 1
   for (int sweep = 0; sweep < VR_SWEEPS; ++sweep) {
-    jacobi_rot<0, 1>(a, v); jacobi_rot<0, 2>(a, v); jacobi_rot<0, 3>(a, v);
-    jacobi_rot<1, 2>(a, v); jacobi_rot<1, 3>(a, v); jacobi_rot<2, 3>(a, v);
+    jacobi_rot<4, 0, 1>(a, v); jacobi_rot<4, 0, 2>(a, v); jacobi_rot<4, 0, 3>(a, v);
+    jacobi_rot<4, 1, 2>(a, v); jacobi_rot<4, 1, 3>(a, v); jacobi_rot<4, 2, 3>(a, v);
   }
   double best = a[0], e[4] = {v[0], v[4], v[8], v[12]};     // w x y z
 #pragma unroll
@@ -224,10 +169,6 @@ __device__ __forceinline__ void point_cov(const VrArgs &A, double x, double y, d
   S[3] = gy * gy * A.s_px2 + hy * hy * v; S[4] = hy * v;
   S[5] = v;
 }
-
-__device__ __forceinline__ bool pivot_ok(double d) { return d > 0 && d < __builtin_huge_val(); }
-__device__ __forceinline__ constexpr int ut6(int r, int c) { return r * 6 - r * (r - 1) / 2 + c - r; }   // upper triangle of a 6x6, by rows
-__device__ __forceinline__ constexpr int lt6(int r, int c) { return r * (r + 1) / 2 + c; }               // lower triangle packed by rows
 
 template <int W>
 __global__ __launch_bounds__(64 * W) void k_vro_ransac(VrArgs A) {
@@ -281,7 +222,7 @@ __global__ __launch_bounds__(64 * W) void k_vro_ransac(VrArgs A) {
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) better(my_cnt, my_h, __shfl_xor(my_cnt, o, 64), __shfl_xor(my_h, o, 64));
-  my_valid = wsum(my_valid);
+  my_valid = wave_sum(my_valid);
   if (lane == 0) { w_cnt[wave] = my_cnt; w_h[wave] = my_h; w_valid[wave] = my_valid; }
   __syncthreads();
   if (wave != 0) return;                           // the last barrier is behind: wave 0 goes on alone
@@ -302,7 +243,7 @@ __global__ __launch_bounds__(64 * W) void k_vro_ransac(VrArgs A) {
       mask[k] = in;
       n_in += in;
     }
-    n_in = wsum(n_in);
+    n_in = wave_sum(n_in);
     for (int round = 0; round < A.refine_rounds; ++round) {
       double s[6] = {0, 0, 0, 0, 0, 0};
       for (int k = lane; k < M; k += 64)
@@ -311,7 +252,7 @@ __global__ __launch_bounds__(64 * W) void k_vro_ransac(VrArgs A) {
           for (int c = 0; c < 3; ++c) { s[c] += xi[3 * k + c]; s[3 + c] += xj[3 * k + c]; }
         }
 #pragma unroll
-      for (int c = 0; c < 6; ++c) s[c] = wsum(s[c]) / (double)n_in;
+      for (int c = 0; c < 6; ++c) s[c] = wave_sum(s[c]) / (double)n_in;
       double C[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
       for (int k = lane; k < M; k += 64)
         if (mask[k]) {
@@ -323,7 +264,7 @@ __global__ __launch_bounds__(64 * W) void k_vro_ransac(VrArgs A) {
             for (int c = 0; c < 3; ++c) C[3 * r + c] += a[r] * b[c];
         }
 #pragma unroll
-      for (int c = 0; c < 9; ++c) C[c] = wsum(C[c]);
+      for (int c = 0; c < 9; ++c) C[c] = wave_sum(C[c]);
       horn(C, q);
       quat_to_R(q, P.R);
 #pragma unroll
@@ -340,8 +281,8 @@ __global__ __launch_bounds__(64 * W) void k_vro_ransac(VrArgs A) {
         mask[k] = in;
         n_new += in;
       }
-      n_in = wsum(n_new);
-      changed = wsum(changed);
+      n_in = wave_sum(n_new);
+      changed = wave_sum(changed);
       if (n_in < A.min_inliers) { status = FGO_VRO_TOO_FEW; break; }
       if (changed == 0) break;
     }
@@ -402,45 +343,46 @@ __global__ __launch_bounds__(64 * W) void k_vro_ransac(VrArgs A) {
 #pragma unroll
           for (int c = r; c < 6; ++c) acc[ut6(r, c)] += Wm[r] * Wm[c] + Wm[6 + r] * Wm[6 + c] + Wm[12 + r] * Wm[12 + c];
       }
-    bad = wsum(bad);
-    ss = wsum(ss);
+    bad = wave_sum(bad);
+    ss = wave_sum(ss);
 #pragma unroll
-    for (int c = 0; c < 21; ++c) info[c] = wsum(acc[c]);
+    for (int c = 0; c < 21; ++c) info[c] = wave_sum(acc[c]);
     rmse = sqrt(ss / (double)n_in);
-    // info = L L^T, cov = L^-T L^-1
+    // info = L L^T, cov = L^-T L^-1: the steps of dev::inv6 with the status seeded by `bad` and the full square as output (kept
+    // here: see small_dense_device.hpp)
     double a[21];
 #pragma unroll
     for (int r = 0; r < 6; ++r)
 #pragma unroll
-      for (int c = 0; c <= r; ++c) a[lt6(r, c)] = info[ut6(c, r)];
+      for (int c = 0; c <= r; ++c) a[lt(r, c)] = info[ut6(c, r)];
     bool ok = bad == 0;
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
-      double d = a[lt6(j, j)];
+      double d = a[lt(j, j)];
 #pragma unroll
-      for (int k = 0; k < j; ++k) d -= a[lt6(j, k)] * a[lt6(j, k)];
+      for (int k = 0; k < j; ++k) d -= a[lt(j, k)] * a[lt(j, k)];
       const bool okj = pivot_ok(d);
       ok = ok && okj;
       const double l = sqrt(okj ? d : 1.0);
-      a[lt6(j, j)] = l;
+      a[lt(j, j)] = l;
 #pragma unroll
       for (int i = j + 1; i < 6; ++i) {
-        double t = a[lt6(i, j)];
+        double t = a[lt(i, j)];
 #pragma unroll
-        for (int k = 0; k < j; ++k) t -= a[lt6(i, k)] * a[lt6(j, k)];
-        a[lt6(i, j)] = t / l;
+        for (int k = 0; k < j; ++k) t -= a[lt(i, k)] * a[lt(j, k)];
+        a[lt(i, j)] = t / l;
       }
     }
     double Mi[21];                                 // L^-1, lower, packed by rows
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
-      Mi[lt6(c, c)] = 1.0 / a[lt6(c, c)];
+      Mi[lt(c, c)] = 1.0 / a[lt(c, c)];
 #pragma unroll
       for (int r = c + 1; r < 6; ++r) {
         double t = 0;
 #pragma unroll
-        for (int k = c; k < r; ++k) t += a[lt6(r, k)] * Mi[lt6(k, c)];
-        Mi[lt6(r, c)] = -t / a[lt6(r, r)];
+        for (int k = c; k < r; ++k) t += a[lt(r, k)] * Mi[lt(k, c)];
+        Mi[lt(r, c)] = -t / a[lt(r, r)];
       }
     }
 #pragma unroll
@@ -449,7 +391,7 @@ __global__ __launch_bounds__(64 * W) void k_vro_ransac(VrArgs A) {
       for (int c = r; c < 6; ++c) {
         double t = 0;
 #pragma unroll
-        for (int k = c; k < 6; ++k) t += Mi[lt6(k, r)] * Mi[lt6(k, c)];
+        for (int k = c; k < 6; ++k) t += Mi[lt(k, r)] * Mi[lt(k, c)];
         cov[6 * r + c] = t;
         cov[6 * c + r] = t;
       }
@@ -482,21 +424,6 @@ __global__ __launch_bounds__(64 * W) void k_vro_ransac(VrArgs A) {
     for (int c = 0; c < 36; ++c) A.cov[36 * pair + c] = cov[c];
   }
 }
-
-// Every device array of a call lives in ONE allocation: a call costs one hipMalloc / hipFree whatever it asks for.  reserve() hands
-// out offsets (256-byte aligned) before the allocation is made, at() turns them into pointers afterwards.
-struct Arena {
-  char *base = nullptr;
-  size_t total = 0;
-  ~Arena() { if (base) (void)hipFree(base); }
-  size_t reserve(size_t bytes) { const size_t o = total; total += (bytes + 255) & ~(size_t)255; return o; }
-  hipError_t alloc() { return hipMalloc((void **)&base, total ? total : 1); }
-  template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(base + off); }
-};
-struct Events {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
 
 int g_waves = VR_DEFAULT_WAVES;
 double g_kernel_ms = 0.0;
@@ -539,42 +466,31 @@ extern "C" int fgo_vro_ransac_batch(int device, int64_t n_pairs, const int64_t *
   if (!(P.sigma_z[0] >= 0) || !(P.sigma_z[1] >= 0) || !(P.sigma_z[2] >= 0) || !(P.sigma_z[0] + P.sigma_z[1] + P.sigma_z[2] > 0)) return FGO_EINVAL;
   if (n_pairs == 0) return FGO_OK;
   if (!match_ptr || !xyz_i || !xyz_j || !pose_ij7_out || !result) return FGO_EINVAL;
-  if (match_ptr[0] < 0) return FGO_EINVAL;
-  for (int64_t p = 0; p < n_pairs; ++p)
-    if (match_ptr[p + 1] < match_ptr[p] || match_ptr[p + 1] - match_ptr[p] > VR_MAX_MATCHES) return FGO_EINVAL;
+  if (!csr_ptr_ok(match_ptr, n_pairs, VR_MAX_MATCHES)) return FGO_EINVAL;
   const int64_t m_total = match_ptr[n_pairs];
   if ((uint64_t)m_total > SIZE_MAX / (3 * sizeof(double))) return FGO_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FGO_ENODEV;   // no CPU fallback
-  if (hipSetDevice(device) != hipSuccess) return FGO_ENODEV;
+  if (int rc = select_device(device)) return rc;
   const size_t n = (size_t)n_pairs, m = (size_t)m_total, D = sizeof(double), K = (size_t)P.hypotheses;
-  Arena M;
-  // inputs (host pointer, bytes), then the outputs (the mask is always there: the kernel works in it)
-  const void *in_host[3] = {match_ptr, xyz_i, xyz_j};
-  const size_t in_bytes[3] = {(n + 1) * sizeof(int64_t), 3 * m * D, 3 * m * D};
-  size_t in_off[3];
-  for (int k = 0; k < 3; ++k) in_off[k] = M.reserve(in_bytes[k]);
-  void *out_host[6] = {pose_ij7_out, info_ut21_out, cov36_out, inlier_out, hyp_count_out, result};
-  const size_t out_bytes[6] = {7 * n * D, 21 * n * D, 36 * n * D, m, n * K * sizeof(int32_t), n * sizeof(fgo_vro_result)};
-  size_t out_off[6];
-  for (int k = 0; k < 6; ++k) out_off[k] = (out_host[k] || k == 3) ? M.reserve(out_bytes[k]) : 0;
-  if (M.alloc() != hipSuccess) return FGO_ENOMEM;
-  for (int k = 0; k < 3; ++k)
-    if (in_bytes[k] && hipMemcpy(M.at<char>(in_off[k]), in_host[k], in_bytes[k], hipMemcpyHostToDevice) != hipSuccess) return FGO_ENUM;
+  // inputs, then the outputs (the mask is always there: the kernel works in it)
+  Staged S;
+  const int h_ptr = S.in(match_ptr, (n + 1) * sizeof(int64_t)), h_xi = S.in(xyz_i, 3 * m * D), h_xj = S.in(xyz_j, 3 * m * D);
+  const int h_pose = S.out(pose_ij7_out, 7 * n * D), h_info = S.out(info_ut21_out, 21 * n * D), h_cov = S.out(cov36_out, 36 * n * D);
+  const int h_mask = S.out(inlier_out, m, true), h_hyp = S.out(hyp_count_out, n * K * sizeof(int32_t));
+  const int h_res = S.out(result, n * sizeof(fgo_vro_result));
+  if (int rc = S.alloc()) return rc;
+  if (int rc = S.upload()) return rc;
   VrArgs A;
   A.n = n_pairs;
-  A.ptr = M.at<int64_t>(in_off[0]); A.xi = M.at<double>(in_off[1]); A.xj = M.at<double>(in_off[2]);
+  A.ptr = S.ptr<int64_t>(h_ptr); A.xi = S.ptr<double>(h_xi); A.xj = S.ptr<double>(h_xj);
   A.K = P.hypotheses; A.refine_rounds = P.refine_rounds; A.min_inliers = P.min_inliers;
   A.seed = P.seed;
   A.max_d2 = P.max_dist * P.max_dist; A.min_side = P.min_side; A.min_area = P.min_side * P.min_side; A.rigid_tol = P.rigid_tol;
   A.fx = P.fx; A.fy = P.fy; A.s_px2 = P.sigma_px * P.sigma_px;
   A.sz0 = P.sigma_z[0]; A.sz1 = P.sigma_z[1]; A.sz2 = P.sigma_z[2];
-  A.pose = M.at<double>(out_off[0]);
-  A.info = info_ut21_out ? M.at<double>(out_off[1]) : nullptr;
-  A.cov = cov36_out ? M.at<double>(out_off[2]) : nullptr;
-  A.mask = M.at<uint8_t>(out_off[3]);
-  A.hyp = hyp_count_out ? M.at<int32_t>(out_off[4]) : nullptr;
-  A.res = M.at<fgo_vro_result>(out_off[5]);
+  A.pose = S.ptr<double>(h_pose); A.info = S.ptr<double>(h_info); A.cov = S.ptr<double>(h_cov);
+  A.mask = S.ptr<uint8_t>(h_mask);
+  A.hyp = S.ptr<int32_t>(h_hyp);
+  A.res = S.ptr<fgo_vro_result>(h_res);
   Events ev;
   if (hipEventCreate(&ev.a) != hipSuccess || hipEventCreate(&ev.b) != hipSuccess) return FGO_ENUM;
   (void)hipEventRecord(ev.a, 0);
@@ -584,8 +500,5 @@ extern "C" int fgo_vro_ransac_batch(int device, int64_t n_pairs, const int64_t *
   if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return FGO_ENUM;
   float ms = 0;
   g_kernel_ms = hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess ? (double)ms : 0.0;
-  for (int k = 0; k < 6; ++k)
-    if (out_host[k] && out_bytes[k] && hipMemcpy(out_host[k], M.at<char>(out_off[k]), out_bytes[k], hipMemcpyDeviceToHost) != hipSuccess)
-      return FGO_ENUM;
-  return FGO_OK;
+  return S.download();
 }

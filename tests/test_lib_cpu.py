@@ -106,6 +106,100 @@ def test_preint_batch_refuses_without_gpu_and_validates():
         assert G.lib.fgo_preint_batch(0, 1, G._i64p(sp), G._dp(acc), G._dp(gyro), 0.005, None, G._dp(params), G._dp(out)) == -2
 
 
+def test_front_end_batches_validate_before_the_device_and_refuse_without_gpu():
+    """the five stand-alone batched front ends decide every FGO_EINVAL, and n == 0 -> FGO_OK, before their first HIP call, so all
+    of that holds without a device; a valid one-record call then gets FGO_ENODEV (no CPU fallback)"""
+    L = G.lib
+    OK, EINVAL, ENODEV = 0, -1, -2
+    no_gpu = L.fgo_device_count() <= 0
+    dec = G._i64p(np.array([0, 2, 1], np.int64))              # a decreasing ptr array (two records)
+    neg = G._i64p(np.array([-1, 1], np.int64))                # a negative ptr[0] (one record)
+
+    # fgo_two_view_ba_batch
+    calib = np.array([250.0, 250.0, 0.0, 90.0, 70.0, 0.0, 0.0, 0.0, 0.0])
+    ptr6 = np.array([0, 6], np.int64)
+    xyz = np.random.default_rng(0).uniform(1.0, 2.0, (6, 3)); uvi = np.zeros((6, 2)); uvj = np.zeros((6, 2))
+    pj = np.zeros((2, 7)); tres = (G.TwoViewResult * 2)()
+
+    def two_view(n, ptr, params=None):
+        return L.fgo_two_view_ba_batch(0, n, ptr, G._dp(xyz), G._dp(uvi), G._dp(uvj), None, G._dp(calib), None, params, G._dp(pj), None,
+                                       None, None, tres)
+    assert L.fgo_two_view_ba_batch(0, 0, None, None, None, None, None, None, None, None, None, None, None, None, None) == OK
+    assert two_view(2, dec) == EINVAL
+    assert two_view(1, neg) == EINVAL
+    tp = G.TwoViewParams(); L.fgo_two_view_params_default(C.byref(tp)); tp.min_matches = 2
+    assert two_view(1, G._i64p(ptr6), C.byref(tp)) == EINVAL
+    if no_gpu:
+        assert two_view(1, G._i64p(ptr6)) == ENODEV
+
+    # fgo_plane_check_vro_batch
+    pose = np.array([[0.0, 0, 0, 0, 0, 0, 1]] * 2); pose0 = np.zeros((2, 7))
+    info = np.zeros((2, 21)); info[:, [0, 6, 11, 15, 18, 20]] = 1.0
+    cov = np.tile(np.eye(6).ravel(), (2, 1))
+    one = np.array([0, 1], np.int64)
+    abcd = np.array([[0.0, 0, 1, 1]] * 2); cov16 = np.tile((1e-4 * np.eye(4)).ravel(), (2, 1))
+    pres = (G.PlaneCheckResult * 2)()
+
+    def plane_check(n, ps, inf, cv, pi_ptr, pj_ptr, params=None):
+        return L.fgo_plane_check_vro_batch(0, n, G._dp(ps), inf, cv, pi_ptr, G._dp(abcd), G._dp(cov16), pj_ptr, G._dp(abcd), G._dp(cov16),
+                                           params, pres, None, None, None, None, None, None)
+    assert L.fgo_plane_check_vro_batch(0, 0, *([None] * 17)) == OK
+    assert plane_check(2, pose, G._dp(info), None, dec, G._i64p(np.array([0, 1, 2], np.int64))) == EINVAL
+    assert plane_check(2, pose, G._dp(info), None, G._i64p(np.array([0, 1, 2], np.int64)), dec) == EINVAL
+    assert plane_check(1, pose, G._dp(info), None, neg, G._i64p(one)) == EINVAL
+    assert plane_check(1, pose, G._dp(info), None, G._i64p(one), neg) == EINVAL
+    assert plane_check(1, pose0, G._dp(info), None, G._i64p(one), G._i64p(one)) == EINVAL
+    assert plane_check(1, pose, G._dp(info), G._dp(cov), G._i64p(one), G._i64p(one)) == EINVAL
+    assert plane_check(1, pose, None, None, G._i64p(one), G._i64p(one)) == EINVAL
+    pp = G.PlaneCheckParams(); L.fgo_plane_check_params_default(C.byref(pp)); pp.d_max = -1.0
+    assert plane_check(1, pose, G._dp(info), None, G._i64p(one), G._i64p(one), C.byref(pp)) == EINVAL
+    if no_gpu:
+        assert plane_check(1, pose, G._dp(info), None, G._i64p(one), G._i64p(one)) == ENODEV
+        assert plane_check(1, pose, None, G._dp(cov), G._i64p(one), G._i64p(one)) == ENODEV
+
+    # fgo_imu_check_vro_batch
+    pm = np.zeros((1, G.PREINT_DOUBLES)); idx = np.zeros(2, np.int64)
+    ires = (G.ImuCheckResult * 2)()
+
+    def imu_check(n, ps, inf, cv, params=None):
+        return L.fgo_imu_check_vro_batch(0, n, G._dp(ps), inf, cv, 1, G._dp(pm), G._i64p(idx), None, None, params, ires, None, None)
+    assert L.fgo_imu_check_vro_batch(0, 0, None, None, None, 0, None, None, None, None, None, None, None, None) == OK
+    assert imu_check(1, pose0, G._dp(info), None) == EINVAL
+    assert imu_check(1, pose, G._dp(info), G._dp(cov)) == EINVAL
+    assert imu_check(1, pose, None, None) == EINVAL
+    ip = G.ImuCheckParams(); L.fgo_imu_check_params_default(C.byref(ip)); ip.d2_gate = 0.0
+    assert imu_check(1, pose, G._dp(info), None, C.byref(ip)) == EINVAL
+    if no_gpu:
+        assert imu_check(1, pose, G._dp(info), None) == ENODEV
+
+    # fgo_vro_ransac_batch
+    xi = np.zeros((6, 3)); xj = np.zeros((6, 3)); vpose = np.zeros((2, 7)); vres = (G.VroResult * 2)()
+
+    def vro(n, ptr, params=None):
+        return L.fgo_vro_ransac_batch(0, n, ptr, G._dp(xi), G._dp(xj), params, G._dp(vpose), None, None, None, None, vres)
+    assert L.fgo_vro_ransac_batch(0, 0, None, None, None, None, None, None, None, None, None, None) == OK
+    assert vro(2, dec) == EINVAL
+    assert vro(1, neg) == EINVAL
+    vp = G.VroParams(); L.fgo_vro_params_default(C.byref(vp)); vp.hypotheses = 0
+    assert vro(1, G._i64p(ptr6), C.byref(vp)) == EINVAL
+    if no_gpu:
+        assert vro(1, G._i64p(ptr6)) == ENODEV
+
+    # fgo_plane_extract_batch
+    depth = np.zeros((4, 4), np.uint16); xres = (G.PlaneExtractResult * 1)()
+    xabcd = np.zeros((G.FGO_PX_MAX_PLANES, 4)); xcov = np.zeros((G.FGO_PX_MAX_PLANES, 16))
+
+    def extract(n, w, params=None):
+        return L.fgo_plane_extract_batch(0, n, w, 4, depth.ctypes.data_as(C.POINTER(C.c_uint16)), params, xres, G._dp(xabcd), G._dp(xcov),
+                                         None, None, None, None)
+    assert L.fgo_plane_extract_batch(0, 0, 4, 4, None, None, None, None, None, None, None, None, None) == OK
+    assert extract(1, 0) == EINVAL
+    xp = G.PlaneExtractParams(); L.fgo_plane_extract_params_default(C.byref(xp)); xp.max_planes = 0
+    assert extract(1, 4, C.byref(xp)) == EINVAL
+    if no_gpu:
+        assert extract(1, 4) == ENODEV
+
+
 def test_exports_are_the_c_abi_only_and_the_allocator_stays_inside():
     """libfgo.so exports the fgo_* entry points and nothing else of its own -- in particular not its operator new / delete
     (csrc/host_alloc.cpp: the library's allocations forward to the process's global operators and add a huge-page hint; a host
