@@ -1161,14 +1161,13 @@ __global__ __launch_bounds__(NW * 64) void k_panel_tri(DevPlan P, const double *
     }
   }
   if (stamp && threadIdx.x == 0) stamp[2] = __builtin_readcyclecounter();
-  for (int gq = gid; lane_on && gq < npair; gq += NW * 10) {
-    const int rr = PAIR_A[gq], kk = PAIR_B[gq];
-    const int t = tb[rr * PM + kk];
-    if (t >= 0) store_row(Lv + 36 * (int64_t)t + 6 * r, load_row(&T[36 * gq + 6 * r]));
-  }
-  // ---- the factored triangle once more, as a dense scalar matrix cut into 16x16 tiles in MFMA A-operand order
-  // (lane l <-> element [l & 15][4 kc + (l >> 4)] of the tile, i.e. column-major): strictly-lower tiles NEGATED,
-  // diagonal tiles INVERTED.  Only the tiles of the nJ tile rows the panel really has are written / read.
+  // ---- Epilogue: the L blocks go to global memory, and the factored triangle once more as a dense scalar matrix cut into
+  // 16x16 tiles in MFMA A-operand order (lane l <-> element [l & 15][4 kc + (l >> 4)] of the tile, i.e. column-major):
+  // strictly-lower tiles NEGATED, diagonal tiles INVERTED.  Only the tiles of the nJ tile rows the panel really has are
+  // written / read.  The inverses are the one dependent chain left after the last pivot.  In the 16-wave form (one or two
+  // panels per level: the launch lasts as long as its chain) they come first and have waves 0 and 1 to themselves, while the
+  // other waves copy the L blocks and the lower tiles out (stores nobody waits for).  The 8-wave throughput form copies
+  // first with all waves, as its register budget (128, two workgroups per CU) has no room for the two roles side by side.
   auto Ls = [&](int i, int j) -> double {
     if (i >= n || j >= n) return (i == j) ? 1.0 : 0.0;          // identity padding up to the tile boundary
     const int rr = i / 6, kk = j / 6;
@@ -1176,31 +1175,51 @@ __global__ __launch_bounds__(NW * 64) void k_panel_tri(DevPlan P, const double *
     return T[TRI(rr, kk) + (i - 6 * rr) * 6 + (j - 6 * kk)];
   };
   double *__restrict__ tp = P.pp.ptop + (int64_t)dsc.top * 256;
-  for (int e = threadIdx.x; e < (nJ * (nJ - 1) / 2) * 256; e += NW * 64) {   // tiles (J, I), I < J < nJ, are the first nJ (nJ-1) / 2
-    const int tile = e >> 8, kc = (e >> 6) & 3, l = e & 63;
-    const int J = PAIR_A[tile] + 1, I = PAIR_B[tile];
-    tp[e] = -Ls(16 * J + (l & 15), 16 * I + 4 * kc + (l >> 4));
-  }
   __shared__ double Dt[NJMAX * 256];                            // the diagonal tiles, staged in LDS (51 KB with the triangle image)
+  __shared__ double Dr[NW >= 16 ? NJMAX * 16 : 1];              // the reciprocals of their diagonals (16-wave form)
+  // lane groups gq0, gq0 + gstep, ... copy the L blocks, threads e0, e0 + estep, ... the elements of the lower tiles
+  auto copy_out = [&](int gq0, int gstep, int e0, int estep) {
+    for (int gq = gq0; lane_on && gq < npair; gq += gstep) {
+      const int rr = PAIR_A[gq], kk = PAIR_B[gq];
+      const int t = tb[rr * PM + kk];
+      if (t >= 0) store_row(Lv + 36 * (int64_t)t + 6 * r, load_row(&T[36 * gq + 6 * r]));
+    }
+    for (int e = e0; e < (nJ * (nJ - 1) / 2) * 256; e += estep) {   // tiles (J, I), I < J < nJ, are the first nJ (nJ-1) / 2
+      const int tile = e >> 8, kc = (e >> 6) & 3, l = e & 63;
+      const int J = PAIR_A[tile] + 1, I = PAIR_B[tile];
+      tp[e] = -Ls(16 * J + (l & 15), 16 * I + 4 * kc + (l >> 4));
+    }
+  };
+  auto invert = [&]() {
+    if ((int)threadIdx.x < 16 * nJ) {                           // column c of the inverse of diagonal tile J, straight to memory
+      const int J = threadIdx.x >> 4, c = threadIdx.x & 15;
+      double xc[16];
+      // column c of Dt^-1 by forward substitution, right-looking: the 16 reciprocals first (independent of the chain; the 16-wave
+      // form computes one per lane of the tile's 16 and shares them through LDS: one division in front of the chain instead of 16
+      // in a lane's instruction stream), then per step one multiply and the updates of the rows below (chain: 2 operations per
+      // row instead of a dot product and a division)
+      const double *__restrict__ D = &Dt[J * 256];
+      if (NW >= 16) {
+        Dr[threadIdx.x] = 1.0 / D[c * 17];
+        __builtin_amdgcn_wave_barrier();                          // (the 16 lanes of a tile are lanes of one wave)
+      }
+#pragma unroll
+      for (int i = 0; i < 16; ++i) xc[i] = (i == c) ? 1.0 : 0.0;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        xc[i] *= NW >= 16 ? Dr[16 * J + i] : 1.0 / D[i * 17];     // (the same correctly rounded quotient either way)
+#pragma unroll
+        for (int i2 = 0; i2 < 16; ++i2) if (i2 > i) xc[i2] = fma(-D[i2 * 16 + i], xc[i], xc[i2]);
+      }
+#pragma unroll
+      for (int i = 0; i < 16; ++i) tp[(NLT + J) * 256 + 16 * c + i] = xc[i];
+    }
+  };
+  if (NW < 16) copy_out(gid, NW * 10, (int)threadIdx.x, NW * 64);
   for (int e = threadIdx.x; e < nJ * 256; e += NW * 64) Dt[e] = Ls(16 * (e >> 8) + ((e >> 4) & 15), 16 * (e >> 8) + (e & 15));
   __syncthreads();
-  if ((int)threadIdx.x < 16 * nJ) {                             // column c of the inverse of diagonal tile J, straight to memory
-    const int J = threadIdx.x >> 4, c = threadIdx.x & 15;
-    double xc[16];
-    // column c of Dt^-1 by forward substitution, right-looking: the 16 reciprocals first (independent), then per step one
-    // multiply and the updates of the rows below (chain: 2 operations per row instead of a dot product and a division)
-    const double *__restrict__ D = &Dt[J * 256];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) xc[i] = (i == c) ? 1.0 : 0.0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      xc[i] *= 1.0 / D[i * 17];                                   // (the reciprocal does not depend on the chain)
-#pragma unroll
-      for (int i2 = 0; i2 < 16; ++i2) if (i2 > i) xc[i2] = fma(-D[i2 * 16 + i], xc[i], xc[i2]);
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) tp[(NLT + J) * 256 + 16 * c + i] = xc[i];
-  }
+  if (NW < 16 || wave < 2) invert();
+  else copy_out(gid - 20, (NW - 2) * 10, (int)threadIdx.x - 128, (NW - 2) * 64);
   if (stamp && threadIdx.x == 0) { stamp[3] = __builtin_readcyclecounter(); stamp[4] = wall_clock64(); }
 }
 
@@ -1792,20 +1811,20 @@ __global__ __launch_bounds__(64) void k_bwd_ext(DevPlan P, const double *__restr
   }
 }
 
+// ---- Shared pieces of the panel backward kernels (k_bwd_tri, k_bwd_fused, k_bwd_chain).
+//
 // In-panel backward substitution x_T = T^-T s from the panel's operand tiles (k_panel_tri): one wave, blocked on the
 // 16x16 tiles.  A tile in operand order is simply column-major (element (i, j) at 16 j + i), so (T_IJ)^T x_I and
 // Dinv_J^T w are dot products of contiguous columns: lane (p, j) takes rows 4p .. 4p+3 of column j, two xor-shuffles
 // finish the sum.  The tiles of tile column J (those below the diagonal + the inverted diagonal tile) are loaded one
-// step ahead of their use.
-__global__ __launch_bounds__(64) void k_bwd_tri(DevPlan P, double *__restrict__ x, int pn0) {
-  __shared__ __attribute__((aligned(16))) double sb[16 * NJMAX], wb[16 * NJMAX], xb[16 * NJMAX];
-  const int pn = pn0 + blockIdx.x;
-  const PanelDesc d = P.pp.pdesc[pn];
-  if (!task_runs(P, d.task)) return;
-  const int n = 6 * d.m, nJ = (n + 15) >> 4;
-  const int *__restrict__ cols = P.task_cols + d.cols0;
-  const int lane = threadIdx.x, j = lane & 15, p = lane >> 4;
-  const double *__restrict__ tp = P.pp.ptop + (int64_t)d.top * 256;
+// step ahead of their use.  IMG: the tiles are read from the workgroup's LDS image (bwd_tiles_to_lds) instead of ptop.
+constexpr int LT_COL = 18, LT_TILE = 16 * LT_COL;      // LDS image of a tile: columns padded to 18 doubles, so that the 16 lanes of a p read 16 different 16-byte slots
+constexpr int NTILE = NLT + NJMAX;                     // tile slots of a panel in ptop: the strictly-lower ones, then the diagonal ones
+template <bool IMG>
+__device__ __forceinline__ void bwd_panel_subst(const double *__restrict__ tp, int nJ, int lane, const double *__restrict__ sb, double *__restrict__ wb,
+                                                double *__restrict__ xb) {
+  constexpr int TS = IMG ? LT_TILE : 256, CS = IMG ? LT_COL : 16;
+  const int j = lane & 15, p = lane >> 4;
   // tile column J: lower tiles (I, J), I = J+1 .. nJ-1, into slots I, the diagonal tile into slot J
   auto load_tile_col = [&](int J, double (&A)[NJMAX][4]) {
 #pragma unroll
@@ -1813,22 +1832,13 @@ __global__ __launch_bounds__(64) void k_bwd_tri(DevPlan P, double *__restrict__ 
       const bool need = I >= J && I < nJ;                      // wave-uniform
       if (need) {
         const int t = I == J ? NLT + J : I * (I - 1) / 2 + J;
-        const double2 lo = *reinterpret_cast<const double2 *>(tp + t * 256 + 16 * j + 4 * p);
-        const double2 hi = *reinterpret_cast<const double2 *>(tp + t * 256 + 16 * j + 4 * p + 2);
+        const double2 lo = *reinterpret_cast<const double2 *>(tp + t * TS + CS * j + 4 * p);
+        const double2 hi = *reinterpret_cast<const double2 *>(tp + t * TS + CS * j + 4 * p + 2);
         A[I][0] = lo.x; A[I][1] = lo.y; A[I][2] = hi.x; A[I][3] = hi.y;
       }
     }
   };
   double Abuf[2][NJMAX][4];
-  for (int c = lane; c < 16 * NJMAX; c += 64) {
-    double s = 0.0;
-    if (c < n) {
-      s = x[6 * (int64_t)cols[c / 6] + (c - 6 * (c / 6))];
-      for (int q = 0; q < d.nchunks; ++q) s -= P.pp.bpart[(int64_t)(d.chunk0 + q) * (6 * PM) + c];
-    }
-    sb[c] = s;
-  }
-  __builtin_amdgcn_wave_barrier();
 #pragma unroll
   for (int J = NJMAX - 1; J >= 0; --J)
     if (J < nJ) {
@@ -1854,165 +1864,241 @@ __global__ __launch_bounds__(64) void k_bwd_tri(DevPlan P, double *__restrict__ 
       if (p == 0) xb[16 * J + j] = a2;
       __builtin_amdgcn_wave_barrier();
     }
-  for (int c = lane; c < n; c += 64) x[6 * (int64_t)cols[c / 6] + (c - 6 * (c / 6))] = xb[c];
 }
 
-
-// Backward solve of a panel in ONE kernel, for levels with few panels (the top of the tree): the 16 waves of the workgroup
-// take the panel's off-triangle rows in chunks of 10 (one row per lane group, as k_bwd_ext), keep their partial sums
-// s_k -= L_ik^T x_i in registers across chunks, combine them through LDS in a fixed order (chunks of a wave, then waves
-// 0 .. 15), and wave 0 finishes with the in-panel substitution x_T = T^-T s from the operand tiles exactly as k_bwd_tri --
-// whose tile loads are issued before the row phase, so they are in flight while the rows are summed.  One launch and no
-// round trip of the partial sums through memory instead of two launches per level.
-constexpr int BWD_NW = 16;
-__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_fused(DevPlan P, const double *__restrict__ Lv, double *__restrict__ x, int pn0) {
-  constexpr int NW = BWD_NW;
-  __shared__ __attribute__((aligned(16))) double slab[NW][60];
-  __shared__ __attribute__((aligned(16))) double wtot[NW][PM * 6];
+__global__ __launch_bounds__(64) void k_bwd_tri(DevPlan P, double *__restrict__ x, int pn0) {
   __shared__ __attribute__((aligned(16))) double sb[16 * NJMAX], wb[16 * NJMAX], xb[16 * NJMAX];
   const int pn = pn0 + blockIdx.x;
   const PanelDesc d = P.pp.pdesc[pn];
-  if (!task_runs(P, d.task)) return;                       // (the wildfire mask: launch_solve passes task_dirty = run, k_wild_mark restores x of a task left out)
-  const int m = d.m, n = 6 * m, nJ = (n + 15) >> 4;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int g = lane / 6, cc = lane - 6 * g;
+  if (!task_runs(P, d.task)) return;
+  const int n = 6 * d.m, nJ = (n + 15) >> 4;
   const int *__restrict__ cols = P.task_cols + d.cols0;
+  const int lane = threadIdx.x;
   const double *__restrict__ tp = P.pp.ptop + (int64_t)d.top * 256;
-  // ---- rows: wave w takes chunks w, w + 16, ... ; lanes 0..5 of every wave accumulate the wave's total per column block
-  double tot[PM];
-#pragma unroll
-  for (int k = 0; k < PM; ++k) tot[k] = 0.0;
-  for (int r0 = 10 * wave; r0 < d.nrows; r0 += 10 * NW) {
-    const bool on = lane < 60 && r0 + g < d.nrows;
-    const int ri = d.prow0 + r0 + (on ? g : 0);
-    const int *__restrict__ rb = P.pp.prow_blk + (int64_t)ri * PM;
-    Row6 xi = {{0, 0, 0, 0, 0, 0}};
-    if (on) xi = load_row(x + 6 * (int64_t)P.pp.prow_idx[ri]);
-    // (16 columns at a time: the block ids of one half are one round trip and 16 registers)
-#pragma unroll
-    for (int kb = 0; kb < PM; kb += 16) {
-      int tb[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) tb[k] = (on && kb + k < m) ? rb[kb + k] : -1;
-#pragma unroll
-      for (int k = 0; k < 16; ++k)
-        if (kb + k < m) {                                    // wave-uniform
-          double c = 0.0;
-          if (tb[k] >= 0) {
-            const double *Lb = Lv + 36 * (int64_t)tb[k] + cc;
-            c = Lb[0] * xi.v[0] + Lb[6] * xi.v[1] + Lb[12] * xi.v[2] + Lb[18] * xi.v[3] + Lb[24] * xi.v[4] + Lb[30] * xi.v[5];
-          }
-          if (lane < 60) slab[wave][lane] = c;
-          __builtin_amdgcn_wave_barrier();
-          if (lane < 6) {
-            double sacc = 0.0;
-#pragma unroll
-            for (int q = 0; q < 10; ++q) sacc += slab[wave][6 * q + lane];
-            tot[kb + k] += sacc;
-          }
-          __builtin_amdgcn_wave_barrier();
-        }
-    }
-  }
-  if (lane < 6) {
-#pragma unroll
-    for (int k = 0; k < PM; ++k) if (k < m) wtot[wave][6 * k + lane] = tot[k];
-  }
-  __syncthreads();
-  if (wave > 0) return;
-  // ---- in-panel substitution (as k_bwd_tri)
-  const int j = lane & 15, p = lane >> 4;
-  auto load_tile_col = [&](int J, double (&A)[NJMAX][4]) {
-#pragma unroll
-    for (int I = 0; I < NJMAX; ++I) {
-      const bool need = I >= J && I < nJ;
-      if (need) {
-        const int t = I == J ? NLT + J : I * (I - 1) / 2 + J;
-        const double2 lo = *reinterpret_cast<const double2 *>(tp + t * 256 + 16 * j + 4 * p);
-        const double2 hi = *reinterpret_cast<const double2 *>(tp + t * 256 + 16 * j + 4 * p + 2);
-        A[I][0] = lo.x; A[I][1] = lo.y; A[I][2] = hi.x; A[I][3] = hi.y;
-      }
-    }
-  };
-  double Abuf[2][NJMAX][4];
   for (int c = lane; c < 16 * NJMAX; c += 64) {
     double s = 0.0;
     if (c < n) {
       s = x[6 * (int64_t)cols[c / 6] + (c - 6 * (c / 6))];
-      for (int w = 0; w < NW; ++w) s -= wtot[w][c];
+      for (int q = 0; q < d.nchunks; ++q) s -= P.pp.bpart[(int64_t)(d.chunk0 + q) * (6 * PM) + c];
     }
     sb[c] = s;
   }
   __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int J = NJMAX - 1; J >= 0; --J)
-    if (J < nJ) {
-      double (&A)[NJMAX][4] = Abuf[J & 1];
-      if (J == nJ - 1) load_tile_col(J, A);
-      if (J > 0) load_tile_col(J - 1, Abuf[(J - 1) & 1]);
-      double acc = 0.0;
-#pragma unroll
-      for (int I = J + 1; I < NJMAX; ++I)
-        if (I < nJ) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) acc += A[I][u] * xb[16 * I + 4 * p + u];
-        }
-      acc += __shfl_xor(acc, 16, WAVE);
-      acc += __shfl_xor(acc, 32, WAVE);
-      if (p == 0) wb[16 * J + j] = sb[16 * J + j] + acc;
-      __builtin_amdgcn_wave_barrier();
-      double a2 = 0.0;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) a2 += A[J][u] * wb[16 * J + 4 * p + u];
-      a2 += __shfl_xor(a2, 16, WAVE);
-      a2 += __shfl_xor(a2, 32, WAVE);
-      if (p == 0) xb[16 * J + j] = a2;
-      __builtin_amdgcn_wave_barrier();
-    }
+  bwd_panel_subst<false>(tp, nJ, lane, sb, wb, xb);
   for (int c = lane; c < n; c += 64) x[6 * (int64_t)cols[c / 6] + (c - 6 * (c / 6))] = xb[c];
+}
+
+// ---- The 16-wave backward solve of a panel (k_bwd_fused, k_bwd_chain) in its parts.
+constexpr int BWD_NW = 16;
+constexpr int BWD_KB = 4;                              // block columns per LDS exchange of the row phase
+constexpr int BWD_ROWBUF = BWD_KB * 60;                // a wave's exchange slab [BWD_KB][60]; its first 6 PM doubles hold the wave's totals afterwards
+static_assert(PM % BWD_KB == 0 && 6 * BWD_KB <= 64 && 6 * PM <= BWD_ROWBUF && 6 * PM <= 128, "row phase layout");
+
+// What a workgroup can fetch before anything of the levels above is known: a wave's first chunk of rows (x index and block
+// ids of one row per lane group) ...
+struct BwdFirst { int idx; int tb[PM]; };
+__device__ __forceinline__ void bwd_first_chunk(const DevPlan &P, const PanelDesc &d, int wave, int lane, BwdFirst &f) {
+  const int g = lane / 6, r0 = 10 * wave;
+  const bool on = lane < 60 && r0 + g < d.nrows;
+  const int ri = d.prow0 + r0 + (on ? g : 0);
+  f.idx = 0;
+#pragma unroll
+  for (int k = 0; k < PM; ++k) f.tb[k] = -1;
+  if (r0 < d.nrows) {
+    const int *__restrict__ rb = P.pp.prow_blk + (int64_t)ri * PM;
+    if (on) f.idx = P.pp.prow_idx[ri];
+#pragma unroll
+    for (int k = 0; k < PM; ++k) f.tb[k] = (on && k < d.m) ? rb[k] : -1;
+  }
+}
+// ... the panel's operand tiles (final once the factor sweep is over), by all threads into the LDS image: the loads are
+// issued together, the LDS writes follow where the caller has other work in between ...
+constexpr int BWD_TILE_REGS = (NTILE * 128 + BWD_NW * 64 - 1) / (BWD_NW * 64);
+struct BwdTiles { double2 v[BWD_TILE_REGS]; };
+__device__ __forceinline__ bool bwd_tile_needed(int e, int nJ) {
+  const int t = e >> 7;                                      // double2 e & 127 of tile slot t
+  return e < NTILE * 128 && (t < nJ * (nJ - 1) / 2 || (t >= NLT && t < NLT + nJ));
+}
+__device__ __forceinline__ void bwd_tiles_load(const double *__restrict__ tp, int nJ, BwdTiles &r) {
+#pragma unroll
+  for (int q = 0; q < BWD_TILE_REGS; ++q) {
+    const int e = (int)threadIdx.x + q * BWD_NW * 64;
+    r.v[q] = double2{0.0, 0.0};
+    if (bwd_tile_needed(e, nJ)) r.v[q] = *reinterpret_cast<const double2 *>(tp + 2 * e);
+  }
+}
+__device__ __forceinline__ void bwd_tiles_to_lds(const BwdTiles &r, int nJ, double *__restrict__ img) {
+#pragma unroll
+  for (int q = 0; q < BWD_TILE_REGS; ++q) {
+    const int e = (int)threadIdx.x + q * BWD_NW * 64, t = e >> 7, w = e & 127;      // column w >> 3, rows 2 (w & 7), 2 (w & 7) + 1
+    if (bwd_tile_needed(e, nJ)) *reinterpret_cast<double2 *>(img + t * LT_TILE + LT_COL * (w >> 3) + 2 * (w & 7)) = r.v[q];
+  }
+}
+// ... and the panel's own right-hand side: its y of the forward solve, which no other panel writes (lane l of wave 0
+// keeps entries l and l + 64 and their offsets in x).
+struct BwdOwn { int64_t off[2]; double y[2]; };
+__device__ __forceinline__ void bwd_own_rhs(const int *__restrict__ cols, int n, int lane, const double *__restrict__ x, BwdOwn &o) {
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int c = lane + 64 * h;
+    o.off[h] = 0; o.y[h] = 0.0;
+    if (c < n) {
+      o.off[h] = 6 * (int64_t)cols[c / 6] + (c - 6 * (c / 6));
+      o.y[h] = x[o.off[h]];
+    }
+  }
+}
+
+// one lane's term of s_k -= L_ik^T x_i: column cc of block t against the lane group's row of x
+__device__ __forceinline__ double bwd_row_term(const double *__restrict__ Lv, int t, int cc, const Row6 &xi) {
+  double c = 0.0;
+  if (t >= 0) {
+    const double *Lb = Lv + 36 * (int64_t)t + cc;
+    c = Lb[0] * xi.v[0] + Lb[6] * xi.v[1] + Lb[12] * xi.v[2] + Lb[18] * xi.v[3] + Lb[24] * xi.v[4] + Lb[30] * xi.v[5];
+  }
+  return c;
+}
+
+// Row phase: wave w takes the panel's off-triangle rows in chunks of 10 (one row per lane group), chunks w, w + 16, ...
+// The ten lane groups' terms of BWD_KB block columns go through the wave's slab in ONE exchange: lane 6 k' + cc sums the ten
+// values of column k' of the batch (q = 0 .. 9 from 0.0, the order of the one-column-per-exchange form) and keeps the wave's
+// running total of that column over the chunks.  On return buf[6 k + cc] holds the wave's total of block column k, entry cc.
+// agent_x: agent-scope loads of x instead of an acquire fence (k_bwd_chain, mode bit 1).
+__device__ __forceinline__ void bwd_rows(const DevPlan &P, const PanelDesc &d, const double *__restrict__ Lv, const double *x, const BwdFirst &f,
+                                         bool agent_x, int wave, int lane, double *__restrict__ buf) {
+  const int m = d.m;
+  const int g = lane / 6, cc = lane - 6 * g;
+  double tot[PM / BWD_KB];
+#pragma unroll
+  for (int b = 0; b < PM / BWD_KB; ++b) tot[b] = 0.0;
+  for (int r0 = 10 * wave; r0 < d.nrows; r0 += 10 * BWD_NW) {
+    const bool first = r0 == 10 * wave;
+    const bool on = lane < 60 && r0 + g < d.nrows;
+    const int ri = d.prow0 + r0 + (on ? g : 0);
+    const int *__restrict__ rb = P.pp.prow_blk + (int64_t)ri * PM;
+    Row6 xi = {{0, 0, 0, 0, 0, 0}};
+    if (on) {
+      const double *xp = x + 6 * (int64_t)(first ? f.idx : P.pp.prow_idx[ri]);
+      if (agent_x) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) xi.v[c] = __hip_atomic_load(xp + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      } else xi = load_row(xp);
+    }
+    int tb[PM];
+#pragma unroll
+    for (int k = 0; k < PM; ++k) tb[k] = first ? f.tb[k] : ((on && k < m) ? rb[k] : -1);
+#pragma unroll
+    for (int k0 = 0; k0 < PM; k0 += BWD_KB)
+      if (k0 < m) {                                          // wave-uniform
+        double c[BWD_KB];
+#pragma unroll
+        for (int u = 0; u < BWD_KB; ++u) c[u] = bwd_row_term(Lv, tb[k0 + u], cc, xi);      // (columns >= m: block id -1, 0.0)
+        if (lane < 60) {
+#pragma unroll
+          for (int u = 0; u < BWD_KB; ++u) buf[60 * u + lane] = c[u];
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (lane < 6 * BWD_KB && k0 + g < m) {               // lane 6 k' + cc: g == k'
+          double sacc = 0.0;
+#pragma unroll
+          for (int q = 0; q < 10; ++q) sacc += buf[60 * g + 6 * q + cc];
+          tot[k0 / BWD_KB] += sacc;
+        }
+        __builtin_amdgcn_wave_barrier();
+      }
+  }
+  if (lane < 6 * BWD_KB) {
+#pragma unroll
+    for (int b = 0; b < PM / BWD_KB; ++b) if (BWD_KB * b + g < m) buf[6 * BWD_KB * b + lane] = tot[b];
+  }
+}
+
+// wave 0, after the workgroup barrier behind bwd_rows: s = own y minus the waves' totals in the order of the waves, then
+// the substitution from the LDS image of the tiles.  Leaves x_T in xb.
+__device__ __forceinline__ void bwd_finish(const double *__restrict__ rowbuf, const double *__restrict__ img, int n, int nJ, int lane, const BwdOwn &o,
+                                           double *__restrict__ sb, double *__restrict__ wb, double *__restrict__ xb) {
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int c = lane + 64 * h;
+    if (c < 16 * NJMAX) {
+      double s = 0.0;
+      if (c < n) {
+        s = o.y[h];
+        for (int w = 0; w < BWD_NW; ++w) s -= rowbuf[w * BWD_ROWBUF + c];
+      }
+      sb[c] = s;
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  bwd_panel_subst<true>(img, nJ, lane, sb, wb, xb);
+}
+
+// Backward solve of a panel in ONE kernel, for levels with few panels (the top of the tree): everything that depends on the
+// structure and the factor alone -- the waves' first chunks of row indices, the panel's own right-hand side, all of its
+// operand tiles (into LDS) -- is requested first, so it is in flight while x of the rows arrives.  Then the 16 waves take
+// the off-triangle rows (bwd_rows), keep their partial sums s_k -= L_ik^T x_i in registers across chunks, combine them
+// through LDS in a fixed order (chunks of a wave, then waves 0 .. 15), and wave 0 finishes with the in-panel substitution
+// x_T = T^-T s (bwd_finish), the arithmetic of k_bwd_tri.  One launch and no round trip of the partial sums through memory
+// instead of two launches per level.  80 KB of LDS: two workgroups per CU.
+__global__ __launch_bounds__(BWD_NW * 64) void k_bwd_fused(DevPlan P, const double *__restrict__ Lv, double *__restrict__ x, int pn0) {
+  __shared__ __attribute__((aligned(16))) double rowbuf[BWD_NW * BWD_ROWBUF];
+  __shared__ __attribute__((aligned(16))) double img[NTILE * LT_TILE];
+  __shared__ __attribute__((aligned(16))) double sb[16 * NJMAX], wb[16 * NJMAX], xb[16 * NJMAX];
+  const int pn = pn0 + blockIdx.x;
+  const PanelDesc d = P.pp.pdesc[pn];
+  if (!task_runs(P, d.task)) return;                       // (the wildfire mask: launch_solve passes task_dirty = run, k_wild_mark restores x of a task left out)
+  const int n = 6 * d.m, nJ = (n + 15) >> 4;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int *__restrict__ cols = P.task_cols + d.cols0;
+  BwdFirst f;
+  bwd_first_chunk(P, d, wave, lane, f);
+  BwdOwn own = {{0, 0}, {0.0, 0.0}};
+  if (wave == 0) bwd_own_rhs(cols, n, lane, x, own);
+  BwdTiles tiles;
+  bwd_tiles_load(P.pp.ptop + (int64_t)d.top * 256, nJ, tiles);
+  bwd_rows(P, d, Lv, x, f, false, wave, lane, rowbuf + wave * BWD_ROWBUF);
+  bwd_tiles_to_lds(tiles, nJ, img);
+  __syncthreads();
+  if (wave > 0) return;
+  bwd_finish(rowbuf, img, n, nJ, lane, own, sb, wb, xb);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) if (lane + 64 * h < n) x[own.off[h]] = xb[lane + 64 * h];
 }
 
 // ---- Backward solve of the TOP LEVELS in one launch.  The ~24 narrow levels of cfg 2 cost ~19 us each as k_bwd_fused launches:
 // ~4 us of launch floor, the descriptor / index / tile round trips, then the dependent part.  Here every panel of those levels
 // is a workgroup of ONE launch, ordered root level first; a workgroup does everything that does not depend on x of the levels
-// above (descriptors, its first tile column) and then waits until the `need` panels above it have published their part of x
-// (one counter, release / acquire at agent scope -- the decoupled look-back idiom).  Workgroups are dispatched in index
-// order and wait only for smaller indices, so the launch cannot deadlock whatever the residency.  Same arithmetic, same
-// order of operations as k_bwd_fused: bit-identical x.
+// above (descriptors, its first chunks of row indices, its own right-hand side, all of its operand tiles into LDS) and then
+// waits until the `need` panels above it have published their part of x (one counter, release / acquire at agent scope --
+// the decoupled look-back idiom).  Behind the wait only x of the ancestors and the L blocks of the rows are loaded.
+// Workgroups are dispatched in index order and wait only for smaller indices, so the launch cannot deadlock whatever the
+// residency: that holds for any LDS footprint, since a workgroup that is not resident yet is never waited for by a resident
+// one (at 80 KB of LDS one or two workgroups share a CU; with more items than slots the later items start as the earlier ones
+// retire and merely lose their head start).  Same arithmetic, same order of operations as k_bwd_fused: bit-identical x.
 __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_chain(DevPlan P, const double *__restrict__ Lv, double *__restrict__ x, int n_items, int mode) {
-  constexpr int NW = BWD_NW;
   const ChainItem it = P.pp.bchain[blockIdx.x];
-  __shared__ __attribute__((aligned(16))) double slab[NW][60];
-  __shared__ __attribute__((aligned(16))) double wtot[NW][PM * 6];
+  __shared__ __attribute__((aligned(16))) double rowbuf[BWD_NW * BWD_ROWBUF];
+  __shared__ __attribute__((aligned(16))) double img[NTILE * LT_TILE];
   __shared__ __attribute__((aligned(16))) double sb[16 * NJMAX], wb[16 * NJMAX], xb[16 * NJMAX];
   const PanelDesc d = P.pp.pdesc[it.pn];
-  const int m = d.m, n = 6 * m, nJ = (n + 15) >> 4;
+  const int n = 6 * d.m, nJ = (n + 15) >> 4;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int g = lane / 6, cc = lane - 6 * g;
   const int *__restrict__ cols = P.task_cols + d.cols0;
-  const double *__restrict__ tp = P.pp.ptop + (int64_t)d.top * 256;
   unsigned *__restrict__ done = P.pp.bchain_done;
-  // first chunk of rows: indices and L values do not depend on the levels above -> requested before the wait
-  const int r00 = 10 * wave;
-  const bool on0 = lane < 60 && r00 + g < d.nrows;
-  const int ri0 = d.prow0 + r00 + (on0 ? g : 0);
-  int idx0 = 0;
-  int tb0[PM];
+  BwdFirst f;
+  bwd_first_chunk(P, d, wave, lane, f);
+  BwdOwn own = {{0, 0}, {0.0, 0.0}};
+  if (wave == 0) bwd_own_rhs(cols, n, lane, x, own);
+  BwdTiles tiles;
+  bwd_tiles_load(P.pp.ptop + (int64_t)d.top * 256, nJ, tiles);
+  if (mode & 4) {                                            // pull the L blocks of the first chunks towards this XCD's L2 while the levels above run
+    const int cc = lane - 6 * (lane / 6);
+    double warm = 0.0;
 #pragma unroll
-  for (int k = 0; k < PM; ++k) tb0[k] = -1;
-  if (r00 < d.nrows) {
-    const int *__restrict__ rb = P.pp.prow_blk + (int64_t)ri0 * PM;
-    if (on0) idx0 = P.pp.prow_idx[ri0];
-#pragma unroll
-    for (int k = 0; k < PM; ++k) tb0[k] = (on0 && k < m) ? rb[k] : -1;
+    for (int k = 0; k < PM; ++k) if (f.tb[k] >= 0) warm += Lv[36 * (int64_t)f.tb[k] + cc];
+    if (warm == 123.456e300) sb[0] = warm;
   }
-  double warm = 0.0;
-  if (mode & 4) {                                            // pull this panel's operands towards this XCD's L2 while the levels above run
-#pragma unroll
-    for (int k = 0; k < PM; ++k) if (tb0[k] >= 0) warm += Lv[36 * (int64_t)tb0[k] + cc];
-    if (wave == 0) for (int e = lane; e < nJ * 32; e += 64) warm += tp[(NLT + (e >> 5)) * 256 + 8 * (e & 31)];
-    if (warm == 123.456e300) slab[0][0] = warm;
-  }
+  bwd_tiles_to_lds(tiles, nJ, img);
   // ---- wait for the levels above
   if (it.need > 0) {
     if (threadIdx.x == 0) {
@@ -2021,108 +2107,17 @@ __global__ __launch_bounds__(BWD_NW * 64) void k_bwd_chain(DevPlan P, const doub
     __syncthreads();
     if (!(mode & 1)) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   }
-  // ---- rows: wave w takes chunks w, w + 16, ... ; lanes 0..5 of every wave accumulate the wave's total per column block
-  double tot[PM];
-#pragma unroll
-  for (int k = 0; k < PM; ++k) tot[k] = 0.0;
-  for (int r0 = 10 * wave; r0 < d.nrows; r0 += 10 * NW) {
-    const bool first = r0 == r00;
-    const bool on = lane < 60 && r0 + g < d.nrows;
-    const int ri = d.prow0 + r0 + (on ? g : 0);
-    const int *__restrict__ rb = P.pp.prow_blk + (int64_t)ri * PM;
-    Row6 xi = {{0, 0, 0, 0, 0, 0}};
-    if (on) {
-      const double *xp = x + 6 * (int64_t)(first ? idx0 : P.pp.prow_idx[ri]);
-      if (mode & 1) {                                      // agent-scope loads instead of an acquire fence (no L2 invalidation)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) xi.v[c] = __hip_atomic_load(xp + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      } else xi = load_row(xp);
-    }
-#pragma unroll
-    for (int kb = 0; kb < PM; kb += 16) {
-      int tb[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) tb[k] = first ? tb0[kb + k] : ((on && kb + k < m) ? rb[kb + k] : -1);
-#pragma unroll
-      for (int k = 0; k < 16; ++k)
-        if (kb + k < m) {                                    // wave-uniform
-          double c = 0.0;
-          if (tb[k] >= 0) {
-            const double *Lb = Lv + 36 * (int64_t)tb[k] + cc;
-            c = Lb[0] * xi.v[0] + Lb[6] * xi.v[1] + Lb[12] * xi.v[2] + Lb[18] * xi.v[3] + Lb[24] * xi.v[4] + Lb[30] * xi.v[5];
-          }
-          if (lane < 60) slab[wave][lane] = c;
-          __builtin_amdgcn_wave_barrier();
-          if (lane < 6) {
-            double sacc = 0.0;
-#pragma unroll
-            for (int q = 0; q < 10; ++q) sacc += slab[wave][6 * q + lane];
-            tot[kb + k] += sacc;
-          }
-          __builtin_amdgcn_wave_barrier();
-        }
-    }
-  }
-  if (lane < 6) {
-#pragma unroll
-    for (int k = 0; k < PM; ++k) if (k < m) wtot[wave][6 * k + lane] = tot[k];
-  }
+  bwd_rows(P, d, Lv, x, f, (mode & 1) != 0, wave, lane, rowbuf + wave * BWD_ROWBUF);
   __syncthreads();
   if (wave > 0) return;
-  // ---- in-panel substitution (as k_bwd_tri)
-  const int j = lane & 15, p = lane >> 4;
-  auto load_tile_col = [&](int J, double (&A)[NJMAX][4]) {
-#pragma unroll
-    for (int I = 0; I < NJMAX; ++I) {
-      const bool need = I >= J && I < nJ;
-      if (need) {
-        const int t = I == J ? NLT + J : I * (I - 1) / 2 + J;
-        const double2 lo = *reinterpret_cast<const double2 *>(tp + t * 256 + 16 * j + 4 * p);
-        const double2 hi = *reinterpret_cast<const double2 *>(tp + t * 256 + 16 * j + 4 * p + 2);
-        A[I][0] = lo.x; A[I][1] = lo.y; A[I][2] = hi.x; A[I][3] = hi.y;
-      }
-    }
-  };
-  double Abuf[2][NJMAX][4];
-  for (int c = lane; c < 16 * NJMAX; c += 64) {
-    double s = 0.0;
-    if (c < n) {
-      s = x[6 * (int64_t)cols[c / 6] + (c - 6 * (c / 6))];
-      for (int w = 0; w < NW; ++w) s -= wtot[w][c];
-    }
-    sb[c] = s;
-  }
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int J = NJMAX - 1; J >= 0; --J)
-    if (J < nJ) {
-      double (&A)[NJMAX][4] = Abuf[J & 1];
-      if (J == nJ - 1) load_tile_col(J, A);
-      if (J > 0) load_tile_col(J - 1, Abuf[(J - 1) & 1]);
-      double acc = 0.0;
-#pragma unroll
-      for (int I = J + 1; I < NJMAX; ++I)
-        if (I < nJ) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) acc += A[I][u] * xb[16 * I + 4 * p + u];
-        }
-      acc += __shfl_xor(acc, 16, WAVE);
-      acc += __shfl_xor(acc, 32, WAVE);
-      if (p == 0) wb[16 * J + j] = sb[16 * J + j] + acc;
-      __builtin_amdgcn_wave_barrier();
-      double a2 = 0.0;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) a2 += A[J][u] * wb[16 * J + 4 * p + u];
-      a2 += __shfl_xor(a2, 16, WAVE);
-      a2 += __shfl_xor(a2, 32, WAVE);
-      if (p == 0) xb[16 * J + j] = a2;
-      __builtin_amdgcn_wave_barrier();
-    }
+  bwd_finish(rowbuf, img, n, nJ, lane, own, sb, wb, xb);
   if (mode & 2) {
-    for (int c = lane; c < n; c += 64) __hip_atomic_store(x + 6 * (int64_t)cols[c / 6] + (c - 6 * (c / 6)), xb[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) if (lane + 64 * h < n) __hip_atomic_store(x + own.off[h], xb[lane + 64 * h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");            // (the stores are acknowledged before the counter moves)
   } else {
-    for (int c = lane; c < n; c += 64) x[6 * (int64_t)cols[c / 6] + (c - 6 * (c / 6))] = xb[c];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) if (lane + 64 * h < n) x[own.off[h]] = xb[lane + 64 * h];
     // ---- publish: this panel's part of x is visible at agent scope before the counter moves; the last panel re-arms the counter
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
   }
@@ -2592,7 +2587,7 @@ void launch_solve(const DevPlan &P, const HostSchedule &H, const double *Lv, con
   // column needs x of its ancestors only (top + own domain), so no communication
   // (distributed: the chain is the replicated top's, part of the PHASE_TOP pass)
   const bool chain = (phase == PHASE_ALL || phase == PHASE_TOP) && H.bchain_low >= 0 && H.bchain_n > 0;
-  static const int chain_mode = (int)tune("bwd_chain_mode", 5);   // 1: agent-scope loads of x instead of an acquire fence (no L2 invalidation), 2: agent-scope stores + store-acknowledge wait instead of the release fence, 4: operands touched before the wait.  cfg 2 backward sweep: no chain 0.799, modes 0 / 1 / 3 / 7: 0.815 / 0.747 / 0.737 / 0.735 ms
+  static const int chain_mode = (int)tune("bwd_chain_mode", 5);   // 1: agent-scope loads of x instead of an acquire fence (no L2 invalidation), 2: agent-scope stores + store-acknowledge wait instead of the release fence, 4: the L blocks of the first row chunks touched before the wait (the operand tiles are always brought on chip there).  cfg 2 backward sweep: no chain 0.799, modes 0 / 1 / 3 / 7: 0.815 / 0.747 / 0.737 / 0.735 ms
   if (cz) { cz->chain_on = chain ? 1 : 0; cz->chain_mode = chain_mode; }
   if (chain) {
     // the progress counter starts every launch at zero whatever happened to the launch before (an aborted launch would leave
