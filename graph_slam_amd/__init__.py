@@ -120,6 +120,33 @@ class PlaneExtractPlane(C.Structure):
 FGO_PX_OK, FGO_PX_NUM = 0, 2
 FGO_PX_MAX_PLANES = 8
 
+
+class PlanePropagateParams(C.Structure):
+    """fgo_plane_propagate_params"""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("z_scale", C.c_double),
+                ("z_min", C.c_double), ("z_max", C.c_double), ("sigma_px", C.c_double), ("sigma_z", C.c_double * 3),
+                ("d_floor", C.c_double), ("intensity_tol", C.c_int), ("keep_ratio", C.c_double), ("rest_ratio", C.c_double)]
+
+
+class PlanePropagateResult(C.Structure):
+    """fgo_plane_propagate_result"""
+    _fields_ = [("status", C.c_int), ("n_planes", C.c_int), ("num_added", C.c_int), ("search_rest", C.c_int)]
+
+
+class PlanePropagatePlane(C.Structure):
+    """fgo_plane_propagate_plane"""
+    _fields_ = [("n_pixels", C.c_int), ("n_seed", C.c_int), ("source", C.c_int), ("reserved", C.c_int), ("rmse", C.c_double),
+                ("centroid", C.c_double * 3)]
+
+
+class PlanePropagatePred(C.Structure):
+    """fgo_plane_propagate_pred"""
+    _fields_ = [("abcd", C.c_double * 4), ("sdj", C.c_double), ("n_prev", C.c_int), ("n_seed", C.c_int), ("kept", C.c_int),
+                ("reserved", C.c_int)]
+
+
+FGO_PP_OK, FGO_PP_NUM = 0, 2
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)     # fgo_allreduce_fn
 
 
@@ -231,6 +258,14 @@ def _load():
                                             C.POINTER(C.c_int8), C.POINTER(C.c_int32)]
     lib.fgo_debug_plane_extract_kernel_ms.restype = C.c_double
     lib.fgo_debug_plane_extract_kernel_ms.argtypes = []
+    lib.fgo_plane_propagate_params_default.restype = None
+    lib.fgo_plane_propagate_params_default.argtypes = [C.POINTER(PlanePropagateParams)]
+    lib.fgo_plane_propagate_batch.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8),
+                                              C.POINTER(C.c_int8), C.POINTER(C.c_int32), dp, dp, C.c_int64, i64p, i64p, dp, dp, dp,
+                                              C.POINTER(PlanePropagateParams), C.POINTER(PlanePropagateResult), dp, dp, dp,
+                                              C.POINTER(PlanePropagatePlane), C.POINTER(PlanePropagatePred), C.POINTER(C.c_int8)]
+    lib.fgo_debug_plane_propagate_kernel_ms.restype = C.c_double
+    lib.fgo_debug_plane_propagate_kernel_ms.argtypes = []
     lib.fgo_add_vec3.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_bias.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_prior_vec3.argtypes = [C.c_void_p, C.c_int64, dp, C.c_double]
@@ -556,6 +591,124 @@ def plane_extract_batch(depth, params=None, want_labels=False, want_hyp_counts=F
         out["labels"] = lab
     if hyp is not None:
         out["hyp_counts"] = hyp
+    return out
+
+
+def plane_propagate_params(**kw):
+    """fgo_plane_propagate_params_default, with the given fields replaced (sigma_z: three coefficients)"""
+    p = PlanePropagateParams()
+    lib.fgo_plane_propagate_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(PlanePropagateParams._fields_):
+            raise TypeError("fgo_plane_propagate_params has no field %r" % k)
+        setattr(p, k, (C.c_double * 3)(*v) if k == "sigma_z" else v)
+    return p
+
+
+def plane_propagate_batch(depth, intensity, labels, n_planes, abcd, cov16, frame_i, frame_j, pose_ij, info=None, cov=None, params=None,
+                          want_labels=True, want_pred=True, want_planes=True, want_ut6=True, device=0):
+    """fgo_plane_propagate_batch: the planes of frame frame_i[p] carried into frame frame_j[p] for every pair in one launch, one
+    workgroup per pair.  The frames: depth (n x H x W uint16), intensity (n x H x W uint8), labels (n x H x W int8: plane_extract_batch's
+    labels, or this call's), n_planes (n), abcd (n x m x 4) and cov16 (n x m x 4 x 4) with m <= FGO_PX_MAX_PLANES (plane_extract_batch's
+    abcd_all / cov16_all).  The pairs: frame_i, frame_j (indices), pose_ij (n_pairs x 7, the pose of frame j in frame i) and either info
+    (n_pairs x 21) or cov (n_pairs x 6 x 6).  Returns a dict of arrays.  Over the pairs: status (FGO_PP_*), n_planes, num_added,
+    search_rest; with the stride FGO_PX_MAX_PLANES per pair (the slots past n_planes are zero): abcd_all, cov16_all, cov_ut6_all,
+    n_pixels, n_seed, source, rmse, centroid (per kept plane) and pred_abcd, sdj, n_prev, pred_n_seed, kept (per PREVIOUS plane); packed,
+    as plane_extract_batch packs them: ptr, abcd, cov16, cov_ut6; and labels (n_pairs x H x W int8: k, -1 free, -2 free without a depth
+    in range, -3 rejected, -4 claimed by a dropped prediction)."""
+    d = np.ascontiguousarray(depth, np.uint16)
+    if d.ndim != 3:
+        raise FgoError("plane_propagate_batch: depth is n x H x W")
+    nf, h, w = d.shape
+    it = np.ascontiguousarray(intensity, np.uint8); lb = np.ascontiguousarray(labels, np.int8)
+    if it.shape != d.shape or lb.shape != d.shape:
+        raise FgoError("plane_propagate_batch: intensity and labels have the shape of depth")
+    npl = np.ascontiguousarray(n_planes, np.int32).reshape(-1)
+    MP = FGO_PX_MAX_PLANES
+    a = np.asarray(abcd, np.float64).reshape(nf, -1, 4); c = np.asarray(cov16, np.float64).reshape(nf, -1, 16)
+    if len(npl) != nf or a.shape[1] != c.shape[1] or a.shape[1] > MP:
+        raise FgoError("plane_propagate_batch: n_planes (n), abcd (n x m x 4) and cov16 (n x m x 16), m <= %d" % MP)
+    a8 = np.zeros((nf, MP, 4)); a8[:, :a.shape[1]] = a
+    c8 = np.zeros((nf, MP, 16)); c8[:, :c.shape[1]] = c
+    fi = np.ascontiguousarray(frame_i, np.int64).reshape(-1); fj = np.ascontiguousarray(frame_j, np.int64).reshape(-1)
+    n = len(fi)
+    ps = np.ascontiguousarray(pose_ij, np.float64).reshape(-1, 7)
+    if (info is None) == (cov is None):
+        raise FgoError("plane_propagate_batch: exactly one of info (n x 21) and cov (n x 6 x 6)")
+    s = np.ascontiguousarray(info if cov is None else cov, np.float64).reshape(-1, 21 if cov is None else 36)
+    if len(fj) != n or len(ps) != n or len(s) != n:
+        raise FgoError("plane_propagate_batch: frame_i, frame_j, pose_ij and info / cov need one entry per pair")
+    if params is None:
+        params = plane_propagate_params()
+    abcd_o = np.zeros((n, MP, 4)); cov16_o = np.zeros((n, MP, 4, 4))
+    ut6 = np.zeros((n, MP, 6)) if want_ut6 else None
+    planes = (PlanePropagatePlane * max(n * MP, 1))() if want_planes else None
+    pred = (PlanePropagatePred * max(n * MP, 1))() if want_pred else None
+    lab = np.zeros((n, h, w), np.int8) if want_labels else None
+    res = (PlanePropagateResult * max(n, 1))()
+    rc = lib.fgo_plane_propagate_batch(device, nf, w, h, d.ctypes.data_as(C.POINTER(C.c_uint16)), it.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                       lb.ctypes.data_as(C.POINTER(C.c_int8)), npl.ctypes.data_as(C.POINTER(C.c_int32)), _dp(a8), _dp(c8),
+                                       n, _i64p(fi), _i64p(fj), _dp(ps), _dp(s) if cov is None else None, None if cov is None else _dp(s),
+                                       C.byref(params), res, _dp(abcd_o), _dp(cov16_o), None if ut6 is None else _dp(ut6), planes, pred,
+                                       None if lab is None else lab.ctypes.data_as(C.POINTER(C.c_int8)))
+    if rc < 0:
+        raise FgoError("fgo_plane_propagate_batch failed: %d" % rc)
+    fields = ("status", "n_planes", "num_added", "search_rest")
+    r = np.frombuffer(res, dtype=np.dtype([(f, "i4") for f in fields]), count=n)
+    out = {k: r[k].copy() for k in fields}
+    out.update(abcd_all=abcd_o, cov16_all=cov16_o)
+    if planes is not None:
+        pl = np.frombuffer(planes, dtype=np.dtype([("n_pixels", "i4"), ("n_seed", "i4"), ("source", "i4"), ("reserved", "i4"), ("rmse", "f8"),
+                                                    ("centroid", "f8", 3)]), count=n * MP).reshape(n, MP)
+        for k in ("n_pixels", "n_seed", "source", "rmse", "centroid"):
+            out[k] = pl[k].copy()
+    if pred is not None:
+        pd = np.frombuffer(pred, dtype=np.dtype([("abcd", "f8", 4), ("sdj", "f8"), ("n_prev", "i4"), ("n_seed", "i4"), ("kept", "i4"),
+                                                  ("reserved", "i4")]), count=n * MP).reshape(n, MP)
+        out.update(pred_abcd=pd["abcd"].copy(), sdj=pd["sdj"].copy(), n_prev=pd["n_prev"].copy(), pred_n_seed=pd["n_seed"].copy(),
+                   kept=pd["kept"].copy())
+    keep = np.arange(MP)[None, :] < out["n_planes"][:, None]
+    out["ptr"] = np.concatenate([[0], np.cumsum(out["n_planes"])]).astype(np.int64)
+    out["abcd"] = abcd_o[keep]; out["cov16"] = cov16_o[keep].reshape(-1, 16)
+    if ut6 is not None:
+        out["cov_ut6_all"] = ut6; out["cov_ut6"] = ut6[keep]
+    if lab is not None:
+        out["labels"] = lab
+    return out
+
+
+def plane_node_batch(depth, intensity, labels, n_planes, abcd, cov16, frame_i, frame_j, pose_ij, info=None, cov=None, params=None,
+                     extract_params=None, device=0):
+    """CGraphGT::predictPlaneNode for every pair, by composition: plane_propagate_batch (part 1), then part 2
+    (gtsam/gtsam_graph.cpp:1043-1077): for the pairs with search_rest != 0 the depth of every pixel of frame j whose label is not -1 is
+    zeroed and plane_extract_batch (extract_params) runs on the result; the new planes are
+    appended after the propagated ones with source = -1, as far as FGO_PX_MAX_PLANES allows.  The reference then merges overlapping
+    planes (CPlaneNode::mergeOverlappedPlanes), which is not in the reference tree and stays out of scope: nothing is merged here.
+    Returns the dict of plane_propagate_batch with n_planes, abcd_all, cov16_all, cov_ut6_all, n_pixels, rmse, centroid, source, ptr,
+    abcd, cov16, cov_ut6 and labels extended (a new plane's pixels carry its slot), n_new (per pair) and `extracted`, the dict of the
+    plane_extract_batch call over the pairs in `rest` (indices), or None when there was none."""
+    out = plane_propagate_batch(depth, intensity, labels, n_planes, abcd, cov16, frame_i, frame_j, pose_ij, info=info, cov=cov, params=params,
+                                device=device)
+    MP = FGO_PX_MAX_PLANES
+    n = len(out["status"])
+    out["n_new"] = np.zeros(n, np.int32); out["rest"] = np.nonzero(out["search_rest"] != 0)[0]; out["extracted"] = None
+    if len(out["rest"]):
+        d = np.ascontiguousarray(depth, np.uint16)[np.asarray(frame_j, np.int64).reshape(-1)[out["rest"]]].copy()
+        d[out["labels"][out["rest"]] != -1] = 0
+        ex = plane_extract_batch(d, params=extract_params, want_labels=True, device=device)
+        out["extracted"] = ex
+        for r, p in enumerate(out["rest"]):
+            k0 = int(out["n_planes"][p]); m = min(int(ex["n_planes"][r]), MP - k0)
+            for f in ("abcd_all", "cov16_all", "cov_ut6_all", "n_pixels", "rmse", "centroid"):
+                out[f][p, k0:k0 + m] = ex[f][r, :m]
+            out["source"][p, k0:k0 + m] = -1
+            for k in range(m):
+                out["labels"][p][ex["labels"][r] == k] = k0 + k
+            out["n_new"][p] = m
+            out["n_planes"][p] = k0 + m
+        keep = np.arange(MP)[None, :] < out["n_planes"][:, None]
+        out["ptr"] = np.concatenate([[0], np.cumsum(out["n_planes"])]).astype(np.int64)
+        out["abcd"] = out["abcd_all"][keep]; out["cov16"] = out["cov16_all"][keep].reshape(-1, 16); out["cov_ut6"] = out["cov_ut6_all"][keep]
     return out
 
 

@@ -1,5 +1,5 @@
 // Host-side plumbing shared by the stand-alone fgo_*_batch entry points (two-view BA, plane check, IMU check, VRO RANSAC, plane
-// extraction): input validators, device selection, and the one device allocation a call stages its arrays in.  An entry point
+// extraction, plane propagation): input validators, device selection, and the one device allocation a call stages its arrays in.  An entry point
 // decides every FGO_EINVAL, and n == 0 -> FGO_OK, with the validators alone, before select_device() makes the first HIP call.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -52,7 +52,7 @@ struct Events {
 // is reserved and ptr() gives NULL -- unless out() is told `always`: the device side is then there for the kernel to work in
 // (scratch, or an output the kernel needs whether or not the caller wants it) and only the copy back is skipped.
 struct Staged {
-  static constexpr int CAP = 16;
+  static constexpr int CAP = 24;
   struct Entry { const void *src; void *dst; size_t bytes, off; bool present; };
   Arena mem;
   Entry e[CAP];

@@ -32,6 +32,7 @@
 #include "device_plan.hpp"
 #include "factors_device.hpp"
 #include "small_dense_device.hpp"
+#include "plane_fit_device.hpp"
 #include "batch_call.hpp"
 
 namespace fgo {
@@ -52,32 +53,6 @@ struct PcArgs {
   int64_t *match;                                  // the per-plane outputs may be NULL
   double *d2, *raw, *pred, *pred_cov, *sdj;
 };
-
-// the 3x3 block (r0, c0) of the symmetric 6x6 held as its upper triangle
-__device__ __forceinline__ M3 block3(const double S[21], int r0, int c0) {
-  M3 B;
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      const int r = r0 + a, c = c0 + b;
-      B.m[a * 3 + b] = r <= c ? S[ut6(r, c)] : S[ut6(c, r)];
-    }
-  return B;
-}
-
-// (a, b, c, d) with the normal normalised, d untouched, and of CPlane::m_CP (4x4 row-major) the upper triangle of the normal block
-// and entry (3, 3)
-struct PlaneIn { V3 n; double d; M3 Sn; double Sd; };
-__device__ __forceinline__ PlaneIn load_plane(const double *__restrict__ abcd, const double *__restrict__ cov16) {
-  PlaneIn P;
-  const double nn = sqrt(abcd[0] * abcd[0] + abcd[1] * abcd[1] + abcd[2] * abcd[2]);
-  P.n = {abcd[0] / nn, abcd[1] / nn, abcd[2] / nn};
-  P.d = abcd[3];
-  P.Sn = {{cov16[0], cov16[1], cov16[2], cov16[1], cov16[5], cov16[6], cov16[2], cov16[6], cov16[10]}};
-  P.Sd = cov16[15];
-  return P;
-}
 
 // B^T S B (u00 u01 u11) of a symmetric 3x3 S
 __device__ __forceinline__ void tangent_cov(const Basis &B, const M3 &S, double u[3]) {
@@ -226,11 +201,7 @@ __global__ __launch_bounds__(64) void k_plane_check(PcArgs A) {
         double *o = A.pred_cov + 9 * g;
         o[0] = pe[0]; o[1] = pe[1]; o[2] = pe[2]; o[3] = pe[1]; o[4] = pe[3]; o[5] = pe[4]; o[6] = pe[2]; o[7] = pe[4]; o[8] = pe[5];
       }
-      if (A.sdj) {
-        const double nt = dot3(P.n, t);
-        const V3 gv = {t.x - P.n.x * nt, t.y - P.n.y * nt, t.z - P.n.z * nt};
-        A.sdj[g] = P.Sd + dot3(P.n, mv(Svv, P.n)) + dot3(gv, mv(P.Sn, gv));
-      }
+      if (A.sdj) A.sdj[g] = predicted_sdj(P, t, Svv);
     }
     __syncthreads();
 

@@ -10,7 +10,7 @@
 //   square as output) and of kernels_two_view.hip (L^-1 and L^-T L^-1 of the 12x12 factor's trailing block, fused with L L^T):
 //   both were tried on chol6_packed / tri6_inverse and both kernels' instruction streams moved, so they keep their own loops
 //   pt_factor  (kernels_two_view.hip)       3x3 that returns L^-1 directly
-//   the 3x3 inverse of kernels_plane_extract.hip and the 3x3 factors of kernels_imu_check.hip / kernels_vro_ransac.hip, which
+//   the 3x3 inverse of plane_fit_device.hpp and the 3x3 factors of kernels_imu_check.hip / kernels_vro_ransac.hip, which
 //   test their pivots with pivot_ok where chol3 tests > 0 only
 //   bsum4      (kernels_gtsam.hip), block_sum (kernels.hip)   one value, one barrier before the read and one after; bsum below
 //   puts its first barrier before the write

@@ -294,6 +294,92 @@ int fgo_plane_extract_batch(int device, int64_t n_frames, int width, int height,
                             int32_t *hyp_count_out /* n x max_planes x hypotheses, may be NULL: for tests and diagnosis */);
 /* development: the kernel time of the last fgo_plane_extract_batch call by HIP events, ms */
 double fgo_debug_plane_extract_kernel_ms(void);
+/* Plane propagation between depth frames, batched: what the reference does frame after frame, on the CPU, in
+ * CGraphGT::predictPlaneNode part 1 with computeSdj, inThisPlane, intensityTol and regionGrow (gtsam/gtsam_graph.cpp:725-1041; called at
+ * gtsam/test_vro_imu_graph.cpp:241,595 and gtsam/test_ba_imu_graph.cpp:253-365) when visual odometry failed and only the IMU's pose
+ * is left -- for n_pairs independent pairs of frames in ONE launch, one workgroup per pair.  The frames (depth words, intensity
+ * bytes, the label image and the planes of fgo_plane_extract_batch or of this call) are given once, n_frames x H x W row-major and
+ * n_frames x FGO_PX_MAX_PLANES planes, of which frame f uses the first n_planes[f]; pair p carries the planes of frame frame_i[p]
+ * into frame frame_j[p].  All arithmetic is in double: the reference's float pixel coordinates (ujf, vjf, du, dv) are NOT reproduced.
+ * T = pose_ij7[p] (t(3) q_xyzw(4), the pose of frame j in frame i, the quaternion normalised on entry), S its covariance in
+ * [omega; v]: cov36[p] as given or info_ut21[p] inverted by the 6x6 Cholesky of fgo_plane_check_vro_batch, exactly one of the two;
+ * only S_t = S[3:6, 3:6] is read (:889).  The planes l = 0 .. n_planes[frame_i] - 1 are taken in order; ONE flag image of frame j is
+ * shared by all of them (:897): a pixel is free, CLAIMED by a plane, or REJECTED.
+ *   prediction  (computeSdj) n normalised on entry, n_j = R^T n, d_j = n.t + d, S_dj = S_di + n^T S_t n + g^T S_ni g, g = (I - n n^T) t,
+ *               S_ni = cov16[0:3, 0:3], S_di = cov16[3][3] standing in for m_E_Sdi: the pred_abcd_out and sdj_out of
+ *               fgo_plane_check_vro_batch.  The predicted plane is not re-oriented.
+ *   in plane    (inThisPlane) with e = fma(n_j.x, x, fma(n_j.y, y, fma(n_j.z, z, d_j))): e^2 <= S_dj or e^2 <= d_floor^2
+ *   seeds       (:941-1017) every pixel of frame i with label == l is back-projected with frame i's depth (the points of
+ *               fgo_plane_extract_batch), carried over, p_j = R^T (p_i - t), and projected, u = fx x / z + cx, v = fy y / z + cy.  A
+ *               point with z <= 0, or with u or v non-finite or of magnitude >= 2^30, seeds nothing (this rule is ours).  The nine
+ *               candidates are ((int)(u + du), (int)(v + dv)), du, dv in {-0.5, 0, 0.5}, truncated toward zero as C does: a
+ *               projection less than a pixel left of or above the image still seeds column or row 0, as in the reference.  A
+ *               candidate inside the image whose flag is free takes frame j's depth z: not z_min < z < z_max -> REJECTED; else
+ *               CLAIMED by l if its back-projection is in the plane and REJECTED if not.  The outcome depends on the pixel and
+ *               the plane alone, so the seed set does not depend on the order of the pixels.  n_seed = the pixels claimed.
+ *   keep        (:1024-1025) the plane goes on iff n_seed > (int)(keep_ratio n_prev), n_prev = its pixels in frame i, the product in
+ *               double.  A plane that fails keeps its claimed pixels in the flag image (the reference never clears them) and gives
+ *               no output plane.
+ *   growth      (regionGrow, kept planes only) the reference's queue computes a unique fixed point, and the result is DEFINED as it:
+ *               the smallest set E that holds the plane's seeds and is closed under: p in E, q a 4-neighbour of p with
+ *               |I(p) - I(q)| <= intensity_tol; then q is in E if q is claimed (by this plane, an earlier one or a dropped one: it
+ *               conducts and does not join), or if q is free and in the plane by frame j's depth (it joins plane l).  No depth-range
+ *               test here (:800-802): a pixel without a return back-projects to the origin.  REJECTED pixels neither join nor
+ *               conduct; a free pixel that fails stays free for later planes (the == of :822 is a no-op, and that is kept).
+ *               n_pixels = n_seed + the pixels that joined.
+ *   refit       (:1031; computeCOVSparse is not in the reference tree, so this is ours) the fit, orientation (d >= 0), rmse, centroid
+ *               and sandwich covariance of fgo_plane_extract_batch on the plane's final pixel set, with frame j's back-projections
+ *               (not the carried-over points the reference collects) and without the reference's down-sampling by 4.  Output slot k
+ *               is the k-th kept plane; plane_out[k].source = l, whose landmark id the caller carries over.
+ *   record      num_added = sum of n_pixels over the kept planes + sum of n_seed over the dropped ones (:1040); search_rest = 0 if
+ *               num_added > (int)(rest_ratio W H), 2 if num_added == 0, 1 otherwise (:1047-1077: nothing to do / extract from the
+ *               whole frame / extract from the free pixels).  label_out: k = the kept plane of slot k, -1 free, -2 free and the depth
+ *               outside (z_min, z_max), -3 REJECTED, -4 claimed by a dropped prediction; with -1 / -2 / k it reads like the label image
+ *               of fgo_plane_extract_batch and can be the `label` of the next pair.  pred_out[l], per PREVIOUS plane: abcd = (n_j, d_j),
+ *               sdj, n_prev, n_seed, kept.  The slots past the last plane are zero.
+ *   status      FGO_PP_NUM: the information is not positive definite, some S_dj is negative or not finite, or a refit is not positive
+ *               definite or not finite: every output of the pair is zero, its labels are -1 / -2 only and search_rest = 2.
+ * Every sum over pixels follows fgo_plane_extract_batch's rule, no atomics: two calls are bit-identical and a pair's result never
+ * depends on the rest of the batch.  Stateless, host arrays in and out; the call holds 24 bytes of scratch per pixel of every
+ * pair on the device, and one more when width height > 65536 (FGO_ENOMEM: split the batch).  FGO_EINVAL (before any HIP call): a
+ * NULL required pointer, both or neither of info_ut21 / cov36, a negative count, width or height < 1 or width height > 2^24, a frame
+ * index outside [0, n_frames), n_planes outside [0, FGO_PX_MAX_PLANES], a zero quaternion, a zero normal among the first n_planes of a
+ * frame, fx / fy / z_scale / sigma_px <= 0, z_min >= z_max, a sigma_z coefficient < 0 or all three zero, d_floor < 0,
+ * intensity_tol < 0, keep_ratio or rest_ratio outside [0, 1]; FGO_ENODEV without a HIP device (no CPU fallback).  n_pairs == 0: FGO_OK. */
+typedef struct {
+  double fx, fy, cx, cy;   /* 250.5773, 250.5773, 90, 70 */
+  double z_scale;          /* 0.001 */
+  double z_min, z_max;     /* 0.1, 5.0  (:992) */
+  double sigma_px;         /* 1.0 */
+  double sigma_z[3];       /* {0.014, 0, 0} */
+  double d_floor;          /* 0.014 m: e^2 <= d_floor^2 is in the plane whatever S_dj  (:753) */
+  int intensity_tol;       /* 5  (:768) */
+  double keep_ratio;       /* 0.7  (:1024) */
+  double rest_ratio;       /* 0.5  (:1046) */
+} fgo_plane_propagate_params;
+void fgo_plane_propagate_params_default(fgo_plane_propagate_params *p);      /* NULL tolerated */
+#define FGO_PP_OK 0
+#define FGO_PP_NUM 2
+typedef struct { int status, n_planes, num_added, search_rest; } fgo_plane_propagate_result;
+typedef struct { int n_pixels, n_seed, source, reserved; double rmse, centroid[3]; } fgo_plane_propagate_plane;
+typedef struct { double abcd[4], sdj; int n_prev, n_seed, kept, reserved; } fgo_plane_propagate_pred;
+int fgo_plane_propagate_batch(int device, int64_t n_frames, int width, int height,
+                              const uint16_t *depth /* n_frames x H x W */, const uint8_t *intensity /* n_frames x H x W */,
+                              const int8_t *label /* n_frames x H x W */, const int32_t *n_planes /* n_frames */,
+                              const double *abcd /* n_frames x FGO_PX_MAX_PLANES x 4 */,
+                              const double *cov16 /* n_frames x FGO_PX_MAX_PLANES x 16 */,
+                              int64_t n_pairs, const int64_t *frame_i /* n_pairs */, const int64_t *frame_j /* n_pairs */,
+                              const double *pose_ij7 /* n_pairs x 7 */,
+                              const double *info_ut21 /* n_pairs x 21, or NULL */, const double *cov36 /* n_pairs x 36, or NULL */,
+                              const fgo_plane_propagate_params *params /* NULL = defaults */,
+                              fgo_plane_propagate_result *result /* n_pairs */,
+                              double *abcd_out /* n_pairs x FGO_PX_MAX_PLANES x 4 */, double *cov16_out /* n_pairs x FGO_PX_MAX_PLANES x 16 */,
+                              double *cov_ut6_out /* n_pairs x FGO_PX_MAX_PLANES x 6, may be NULL */,
+                              fgo_plane_propagate_plane *plane_out /* n_pairs x FGO_PX_MAX_PLANES, may be NULL */,
+                              fgo_plane_propagate_pred *pred_out /* n_pairs x FGO_PX_MAX_PLANES, may be NULL */,
+                              int8_t *label_out /* n_pairs x H x W, may be NULL */);
+/* development: the kernel time of the last fgo_plane_propagate_batch call by HIP events, ms */
+double fgo_debug_plane_propagate_kernel_ms(void);
 /* utils::chi2(dof, alpha) = boost::math::quantile(chi_squared(dof), alpha) (gtsam/chi2.h:17-26): the x with P(dof / 2, x / 2) = p, P the
  * regularised lower incomplete gamma function (series below x = a + 1, continued fraction above), inverted by a safeguarded Newton
  * iteration from the Wilson-Hilferty start.  Host only.  dof < 1: 0 (as the reference returns); p <= 0: 0; p >= 1: +inf; p NaN: NaN. */
