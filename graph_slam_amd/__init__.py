@@ -206,6 +206,7 @@ def _load():
     lib.fgo_marginal_cov_all.argtypes = [C.c_void_p, C.c_int64, i64p, dp]
     lib.fgo_marginal_cov_pairs.argtypes = [C.c_void_p, C.c_int64, i64p, i64p, dp]
     lib.fgo_debug_selinv_stats.argtypes = [C.c_void_p, dp]
+    lib.fgo_debug_selinv_census.argtypes = [C.c_void_p, i64p]
     lib.fgo_gate_edges_se3.argtypes = [C.c_void_p, C.c_int64, i64p, i64p, dp, dp, C.c_int, dp, dp, dp]
     lib.fgo_edge_chi2_se3.argtypes = [C.c_void_p, C.c_int64, C.c_int64, dp]
     lib.fgo_debug_gate_stats.argtypes = [C.c_void_p, dp]
@@ -973,6 +974,16 @@ class Graph:
         self._chk(lib.fgo_debug_selinv_stats(self._h, _dp(out)))
         return dict(t_lists_s=out[0], list_bytes=int(out[1]), ms_factor=out[2], ms_prep=out[3], ms_sweep=out[4], entries=int(out[5]),
                     fallback_pairs=int(out[6]))
+
+    def selinv_census(self):
+        """what a selected inversion of the built structure launches (fgo_debug_selinv_census; nothing runs): per sweep form
+        ('w16', 'w4') launches, workgroups, columns, max_m, wrap_cols (m > 160 / 40) and max_task_cols; nb, empty_cols (m == 0),
+        prep_workgroups and the device's compute units"""
+        out = np.zeros(16, np.int64)
+        self._chk(lib.fgo_debug_selinv_census(self._h, _i64p(out)))
+        keys = ("launches", "workgroups", "columns", "max_m", "wrap_cols", "max_task_cols")
+        return dict(w16=dict(zip(keys, (int(v) for v in out[0:6]))), w4=dict(zip(keys, (int(v) for v in out[6:12]))),
+                    nb=int(out[12]), empty_cols=int(out[13]), prep_workgroups=int(out[14]), cus=int(out[15]))
 
     def gate_edges(self, a, b, meas7, info21, tangent_order=FGO_TANGENT_G2O, want_cov=False):
         """(d2, chi2[, P]) of candidate SE3 edges a[k] -> b[k] at the current estimate; nothing is added to the graph.

@@ -256,6 +256,13 @@ constexpr int PANEL_ROWS = 10;   // off-triangle rows per workgroup of the panel
 // panel levels with more panels than this run the 8-wave k_panel_tri (two workgroups per CU); the others the 16-wave one,
 // whose launches can carry rider workgroups
 inline int tri_wide_panels(int cus) { return (int)tune("tri_wide", cus); }
+// selected inversion (kernels_sinv.hip): a level of the reverse sweep with fewer tasks than the device has compute units runs
+// 16-wave workgroups (160 lane groups of 6 per column), a wider one 4-wave workgroups (40); k_sinv_prep packs SINV_PREP_COLS
+// columns into a 256-thread workgroup.  The launchers and fgo_debug_selinv_census both go through these.
+inline int sinv_sweep_waves(int n_tasks, int cus) { return n_tasks < (int)tune("sinv_wide", cus) ? 16 : 4; }
+constexpr int SINV_WAVE_GROUPS = 10;   // lane groups of 6 per wave, lanes 60..63 idle
+constexpr int SINV_PREP_COLS = 42;     // lane groups of 6 in a 256-thread workgroup of k_sinv_prep
+inline int sinv_prep_workgroups(int nb) { return (nb + SINV_PREP_COLS - 1) / SINV_PREP_COLS; }
 constexpr int ACC_LONG_OPS = 64;  // an accumulate target with more external ops than this gets a whole workgroup
 constexpr int LEAF_BLOCKS = 168;  // blocks of L a light sub-tree may have (LDS of the leaf kernel): swept on the round-4 schedule, 120 / 144 / 156 / 168 / 176 / 216 -> cfg 2 162.5 / 161.0 / 163.0 / 163.4 / 161.5 / ~159 it/s, cfg 4 factor sweep 2.97 (144) / 2.93 (168) / 3.09 (176) ms, cfg 5 38.7 (144) / 39.0 (168)
 constexpr int LEAF_OPS = 3500;    // update ops a light sub-tree may have (4 B each in LDS next to its blocks: 2 workgroups per CU stay possible)

@@ -355,6 +355,40 @@ int fgo_debug_selinv_stats(const fgo_ctx *c, double out[7]) {
   return FGO_OK;
 }
 
+// tests: what a selected inversion of the built structure launches (see include/fgo.h).  Host tables only; the form of a level
+// is asked of sinv_sweep_waves, as launch_sinv_sweep asks it
+int fgo_debug_selinv_census(const fgo_ctx *c, int64_t out[16]) {
+  if (!c || !out) return FGO_EINVAL;
+  if (c->structure_dirty || c->shard_world > 1) return FGO_ESTATE;
+  const Symbolic &S = c->S;
+  const HostSchedule &H = c->sched;
+  std::fill(out, out + 16, (int64_t)0);
+  for (int l = H.n_levels - 1; l >= 0; --l) {
+    const int t0 = H.level_ptr[l], nt = H.level_ptr[l + 1] - t0;
+    if (nt <= 0) continue;
+    const int waves = sinv_sweep_waves(nt, H.cus);
+    int64_t *o = out + (waves == 16 ? 0 : 6);
+    o[0] += 1;
+    o[1] += nt;
+    for (int t = t0; t < t0 + nt; ++t) {
+      const int ncols = S.task_ptr[t + 1] - S.task_ptr[t];
+      o[2] += ncols;
+      o[5] = std::max<int64_t>(o[5], ncols);
+      for (int ci = S.task_ptr[t]; ci < S.task_ptr[t + 1]; ++ci) {
+        const int j = S.task_cols[ci];
+        const int64_t m = S.colptr[j + 1] - S.colptr[j] - 1;
+        o[3] = std::max(o[3], m);
+        o[4] += m > waves * SINV_WAVE_GROUPS ? 1 : 0;
+      }
+    }
+  }
+  out[12] = S.nb;
+  for (int j = 0; j < S.nb; ++j) out[13] += S.colptr[j + 1] - S.colptr[j] == 1 ? 1 : 0;
+  out[14] = sinv_prep_workgroups(S.nb);
+  out[15] = H.cus;
+  return FGO_OK;
+}
+
 }  // extern "C"
 
 namespace {

@@ -21,7 +21,7 @@ namespace fgo {
 
 namespace {
 
-constexpr int PREP_G = 42;      // lane groups of 6 in a 256-thread workgroup of k_sinv_prep
+constexpr int PREP_G = SINV_PREP_COLS;
 
 __global__ __launch_bounds__(256) void k_sinv_prep(SinvPlan Q, const double *__restrict__ Lv, double *__restrict__ U) {
   __shared__ double sD[PREP_G * 36];
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void k_sinv_prep(SinvPlan Q, const double *__r
 
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void k_sinv_sweep(SinvPlan Q, int task0) {
-  constexpr int G = NW * 10;                          // lane groups of 6: 10 per wave, lanes 60..63 idle
+  constexpr int G = NW * SINV_WAVE_GROUPS;            // lane groups of 6: 10 per wave, lanes 60..63 idle
   __shared__ double sred[G * 36];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int gl = lane / 6, r = lane - 6 * gl;
@@ -167,11 +167,12 @@ __global__ __launch_bounds__(256) void k_sinv_rows(const int *__restrict__ cols,
 }  // namespace
 
 void launch_sinv_prep(const SinvPlan &Q, const double *Lv, double *U, hipStream_t s) {
-  if (Q.nb > 0) hipLaunchKernelGGL(k_sinv_prep, dim3((Q.nb + PREP_G - 1) / PREP_G), dim3(256), 0, s, Q, Lv, U);
+  if (Q.nb > 0) hipLaunchKernelGGL(k_sinv_prep, dim3(sinv_prep_workgroups(Q.nb)), dim3(256), 0, s, Q, Lv, U);
 }
 
 // levels from the root down; a level with fewer tasks than the device has compute units gets 16-wave workgroups (the
-// columns near the root have the longest patterns and nothing else runs beside them), a wide one 4-wave workgroups.
+// columns near the root have the longest patterns and nothing else runs beside them), a wide one 4-wave workgroups
+// (sinv_sweep_waves, which fgo_debug_selinv_census asks too; FGO_TUNE sinv_wide moves the threshold).
 // (Measured at config 2: 8-wave workgroups with four or eight terms of a gather in flight were slower -- sweep 70.2 / 67.4 ms
 // against 55.4 ms: the narrow levels need lane groups for more targets of a column more than deeper pipelining of each.
 // Two targets per lane group, every U element loaded feeding both, was slower too: 59.3 ms.)
@@ -179,7 +180,7 @@ void launch_sinv_sweep(const SinvPlan &Q, const HostSchedule &H, hipStream_t s) 
   for (int l = H.n_levels - 1; l >= 0; --l) {
     const int t0 = H.level_ptr[l], nt = H.level_ptr[l + 1] - t0;
     if (nt <= 0) continue;
-    if (nt < H.cus) hipLaunchKernelGGL(k_sinv_sweep<16>, dim3(nt), dim3(16 * 64), 0, s, Q, t0);
+    if (sinv_sweep_waves(nt, H.cus) == 16) hipLaunchKernelGGL(k_sinv_sweep<16>, dim3(nt), dim3(16 * 64), 0, s, Q, t0);
     else hipLaunchKernelGGL(k_sinv_sweep<4>, dim3(nt), dim3(4 * 64), 0, s, Q, t0);
   }
 }

@@ -627,6 +627,13 @@ int fgo_marginal_cov_pairs(fgo_ctx *ctx, int64_t n, const int64_t *id_a, const i
  * factorisation, [3] of the prep kernel, [4] of the reverse sweep, [5] pair-table entries, [6] pairs of the last
  * fgo_marginal_cov_pairs call that were off the factor's pattern (served by column solves) */
 int fgo_debug_selinv_stats(const fgo_ctx *ctx, double out[7]);
+/* what a selected inversion of the built structure launches, from the host's column patterns, task tables and level schedule
+ * (nothing is launched; FGO_ESTATE before the structure is built).  The reverse sweep runs a level as 16-wave workgroups (G = 160
+ * lane groups per column) or 4-wave ones (G = 40): [0..5] for the 16-wave form, [6..11] for the 4-wave form: launches, workgroups
+ * (= tasks), columns, largest m (off-diagonal blocks of a column), columns with m > G (the target loop wraps), most columns in
+ * one task.  [12] block columns nb, [13] columns with m == 0, [14] workgroups of the prep kernel, [15] compute units of the device
+ * (a level with fewer tasks than FGO_TUNE sinv_wide, by default this count, takes the 16-wave form). */
+int fgo_debug_selinv_census(const fgo_ctx *ctx, int64_t out[16]);
 /* ---- validating an edge BEFORE it enters the graph, inspecting edges afterwards.  The reference asks "is this constraint
  *      consistent with the map, given how uncertain the map is?" in several places and approximates the answer each time, because
  *      a Marginals object costs it a batch factorisation: the chi2_for_vro switch gates a visual-odometry edge with
