@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <vector>
+#include "fgo_internal.hpp"
 
 namespace fgo {
 
@@ -44,6 +45,17 @@ struct RowChunk { int pn, m, s0, R6, prow0, cols0, top, task; };                
 struct BwdChunk { int pn, m, row0, nrows; };                                    // <= PANEL_ROWS block rows (absolute row0)
 struct ChainItem { int pn, need; };                                             // k_bwd_chain: panel + panels of the levels above it (all must be done first)
 
+// Operand tiles of a panel (PanelPlan::ptop).  The triangle kernels (k_panel_tri*, kernels_factor.hip) leave a panel's factored dense
+// triangle -- 6 m <= 6 PANEL_MAX scalar columns -- behind as 16x16 tiles of 256 doubles in MFMA A-operand order (column-major), NTILE slots
+// per panel from PanelDesc::top on: first the NLT strictly-lower tiles (J, I), I < J, at slot J (J - 1) / 2 + I, NEGATED, then the NJMAX
+// diagonal tiles at slot NLT + J, INVERTED.  k_panel_rows* and the panel solves (k_fwd_tri, k_bwd_tri, k_bwd_fused, k_bwd_chain,
+// kernels_solve.hip) read them through the same numbers; fgo_structure.cpp sizes the buffer from them.
+constexpr int NJMAX = (6 * PANEL_MAX + 15) / 16;       // 16-wide tile rows of a panel's dense scalar triangle
+constexpr int NLT = NJMAX * (NJMAX - 1) / 2;           // strictly-lower tiles
+constexpr int NTILE = NLT + NJMAX;                     // tile slots of a panel in ptop: the strictly-lower ones, then the diagonal ones
+constexpr int PTOP_TILE = 256;                         // doubles per tile
+static_assert(NTILE == NJMAX * (NJMAX + 1) / 2, "ptop: one slot per tile of the lower triangle, diagonal included");
+
 // panels (fgo_internal.hpp, Symbolic): descriptors of the supernode-like column paths at the top of the tree
 struct PanelPlan {
   const PanelDesc *pdesc;
@@ -65,7 +77,7 @@ struct PanelPlan {
   const int *rchunk_src;          // [row chunks from rchunk_src0 on][16 scalar rows][PANEL_MAX]: prow_src of the chunk's rows (the right-hand-side row: its columns), -1 beyond:
   int rchunk_src0;                //   addressed by the CHUNK, so the row kernel of the NARROW levels requests it beside the chunk's descriptor (one dependent round trip less)
   const int *ptri_src, *prow_src; // like ptri_blk / prow_blk: >= 0 value in L block, <= -2 value in H block -2-x, -1 zero
-  double *ptop;                   // [panels of panel levels][NJ (NJ+1)/2 tiles of 256] factored triangles as MFMA operand tiles (k_panel_tri)
+  double *ptop;                   // [panels of panel levels][NTILE][PTOP_TILE] factored triangles as MFMA operand tiles (above)
   double *fpart;                  // [n_fchunks][6]   partial forward sums
   double *bpart;                  // [n_pchunks][PM][6] partial backward sums
 };
@@ -201,7 +213,7 @@ struct DevPlan {
   const int *g2_task;           // [groups] task of every column-group of k_chol_acc2
   const int *tcol_task;         // [nb] task of every entry of task_cols
   BaPlan ba;                    // landmark elimination (n_lm == 0: off)
-  // forward-solve work items of the accumulate launches (kernels.hip fwd_role): entry of task_cols + chunk of its row (-1: whole
+  // forward-solve work items of the accumulate launches (kernels_factor.hip fwd_role): entry of task_cols + chunk of its row (-1: whole
   // row); per entry of task_cols: first chunk / chunks of the row (when it is split)
   const int *fwg_ci, *fwg_ch;
   const int *fwd_f0, *fwd_fn;
@@ -277,7 +289,7 @@ struct PartialSweep {
   const int *g0, *g1, *c0, *c1;
   const int *task_ptr;
 };
-// ---- launch selection.  Which instantiation a level runs is decided by pure host functions of the schedule (select_*, kernels.hip);
+// ---- launch selection.  Which instantiation a level runs is decided by pure host functions of the schedule (select_*, launch_select.cpp);
 // the launchers switch on the enumerator they return, and a census (fgo_debug_launch_census) walks the same launchers with the
 // launches switched off, so tests can assert which form a threshold sends a level to.  The thresholds live in select_* only.
 enum LaunchForm {
@@ -316,7 +328,7 @@ LaunchForm select_bwd(const HostSchedule &H, int l);       // panel level: LF_BW
 void launch_factor(const DevPlan &P, const HostSchedule &H, const double *Hblk, double *Lv, const double *lambda_p,
                    int *fail_flag, hipStream_t s, const double *b = nullptr, double *x = nullptr, int phase = PHASE_ALL, const PartialSweep *ps = nullptr,
                    const double *b_full = nullptr, LaunchCensus *census = nullptr);   // (b_full: distributed landmark elimination, see k_dist_rhs)
-// wildfire back-substitution (kernels.hip k_wild_*): device arrays per task (run, dirty) / per column (chg), the previous solution
+// wildfire back-substitution (kernels_solve.hip k_wild_*): device arrays per task (run, dirty) / per column (chg), the previous solution
 struct Wildfire { unsigned char *run, *chg; const unsigned char *dirty; const double *xprev; double thr; };
 void launch_solve(const DevPlan &P, const HostSchedule &H, const double *Lv, const double *b, double *x, hipStream_t s,
                   bool fwd_done = false, int phase = PHASE_ALL, const Wildfire *wf = nullptr, LaunchCensus *census = nullptr);

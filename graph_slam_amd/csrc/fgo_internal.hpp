@@ -160,6 +160,10 @@ inline void parallel_ranges(int n, int chunk, F &&fn) {
 // A rider item: ops [o0, o0 + n) of target block t, applied by spare workgroups of a k_panel_tri launch of an EARLIER level
 // (symbolic.cpp "riders"); first = the target starts from H (+ lambda), otherwise from its partial value in L
 struct RideItem { int t, task; long long o0; int n, first; };   // first: 1 = start from H (+ lambda), 0 = from the value in L, 2 = a hub target's piece: t is a scratch block, it receives + sum L_a L_b^T
+// Rider items per rider workgroup of a 16-wave k_panel_tri launch (ride_items16, kernels_factor.hip: four waves per item); symbolic.cpp
+// sorts the items inside the XCD-contiguous ranges those workgroups take.  (Here and not in device_plan.hpp: symbolic.cpp is also built
+// without the HIP headers.)
+constexpr int RIDE_PER_WG = 4;
 
 // undirected block graph of the free poses (CSR, no self loops, no duplicates)
 struct BlockGraph {

@@ -1086,20 +1086,19 @@ struct StructureBuild {
     std::vector<int> task_level((size_t)S.task_ptr.size() - 1, 0);
     for (size_t l = 0; l + 1 < S.level_ptr.size(); ++l)
       for (int t = S.level_ptr[l]; t < S.level_ptr[l + 1]; ++t) task_level[t] = (int)l;
-    // operand tiles only for panels that run the panel kernels; PanelDesc::top = the panel's first tile (of 256 doubles) in ptop:
-    // NJ (NJ + 1) / 2 = 21 tiles for the NJ = ceil(6 x 16 / 16) tile rows of a 16-column panel
+    // operand tiles only for panels that run the panel kernels; PanelDesc::top = the panel's first tile in ptop (device_plan.hpp: NTILE
+    // slots of PTOP_TILE doubles per panel)
     int64_t n_tiles = 0;
     for (int pn = 0; pn < S.n_panels; ++pn) {
       const int t = S.panel_task[pn];
       const int rows = S.prow_ptr[pn + 1] - S.prow_ptr[pn];
-      constexpr int NJ = (6 * PANEL_MAX + 15) / 16;
       const bool has = S.level_panel[task_level[t]];
       pd[pn] = PanelDesc{t, S.task_ptr[t + 1] - S.task_ptr[t], S.task_ptr[t], S.prow_ptr[pn], rows, S.panel_chunk0[pn],
                          (rows + PANEL_ROWS - 1) / PANEL_ROWS, has ? (int)n_tiles : -1};
-      if (has) n_tiles += NJ * (NJ + 1) / 2;
+      if (has) n_tiles += NTILE;
     }
     if (n_tiles > INT32_MAX) return fail(c, FGO_ENOMEM, "operand-tile table too large");
-    HIPCHK(c, c->d_ptop.alloc((size_t)n_tiles * 256));
+    HIPCHK(c, c->d_ptop.alloc((size_t)n_tiles * PTOP_TILE));
     std::vector<RowChunk> rc(S.rchunk_panel.size());
     for (size_t q = 0; q < rc.size(); ++q) {
       const PanelDesc &d = pd[S.rchunk_panel[q]];

@@ -2,7 +2,7 @@
 // What the reference builds: Pose3 keyframes + Point3 landmarks + GenericProjectionFactor<Pose3, Point3, Cal3DS2> with
 // body_P_sensor + priors (gtsam/gtsam_graph.cpp:370-448, 500-610), optimised by LevenbergMarquardtOptimizer (:1784-1788).
 // A landmark couples to ~10 cameras and to nothing else, so it is eliminated analytically -- 3x3 blocks, 6x3 couplings, no
-// padding to 6x6 -- and only the cameras form the block system that the sparse Cholesky (kernels.hip) factors:
+// padding to 6x6 -- and only the cameras form the block system that the sparse Cholesky (kernels_factor.hip) factors:
 //   k_ba_linearize   per landmark: residuals / Jacobians of its observations -> H_pp, b_p, chi2
 //   k_ba_cameras     per camera: its observations again -> H_cc, b_c contributions and W = J_c^T w J_p per observation
 //   k_ba_points      per landmark and LM trial: L_pp = chol(H_pp + lambda I), y_p = L_pp^-1 b_p

@@ -5,7 +5,7 @@
 //   OrientedPlane3Factor                           :1265
 //   GenericProjectionFactor<Pose3,Point3,Cal3DS2>  :405-409
 // Variables of every kind are 6-blocks (3-dof ones padded with an identity diagonal), so the block-sparse
-// Cholesky and the solves (kernels.hip) are shared with the g2o path unchanged.
+// Cholesky and the solves (kernels_factor.hip, kernels_solve.hip) are shared with the g2o path unchanged.
 // Same gather-form assembly as k_linearize: every H block written once by one lane group, no FP atomics.
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -4,7 +4,7 @@
 //
 // Near-relatives that are NOT here, because their storage or pivot rule differs and different rules mean different code:
 //   chol6      (kernels_gate.hip)           full 36-entry storage with the zeros above the diagonal written, functor input, pivot > 0
-//   chol6_lds  (kernels.hip)                the factor sweep's 6x6 block read from LDS: right-looking, rsqrt, returns 1 / L_jj
+//   chol6_lds  (kernels_factor.hip)         the factor sweep's 6x6 block read from LDS: right-looking, rsqrt, returns 1 / L_jj
 //   chol12     (kernels_two_view.hip)       12x12, multiplies by 1 / l, no unit pivot on failure
 //   the 6x6 covariance of kernels_vro_ransac.hip (the steps of inv6 with the status seeded by the wave's `bad` flag and the full
 //   square as output) and of kernels_two_view.hip (L^-1 and L^-T L^-1 of the 12x12 factor's trailing block, fused with L L^T):

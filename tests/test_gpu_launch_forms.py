@@ -1,6 +1,6 @@
 """Every instantiation that launch_factor / launch_fwd_level / launch_solve can select, pinned to a dense solve.
 
-The launch selection (kernels.hip select_*) goes by thresholds on level width that were tuned on 100k- and 1M-pose graphs; graphs
+The launch selection (launch_select.cpp select_*) goes by thresholds on level width that were tuned on 100k- and 1M-pose graphs; graphs
 small enough for a dense reference reach a handful of the forms on their own.  Here FGO_TUNE override sets move the thresholds so
 that each form runs on small graphs whose panels have every width 1..16 and whose lists end in ragged remainders, the launch
 census (fgo_debug_launch_census) proves that the form a set is named for really ran, and both the stand-alone solve
@@ -75,7 +75,7 @@ SETS = [
 SET_NAMES = [s[0] for s in SETS]
 # sets whose results the code claims to be the same to the bit (fgo_internal.hpp: the column-group lists apply a target's updates in
 # the order of the gather lists -- one wave per group against one wave per ten targets, no riders and no long-list role, which
-# sum a list in pieces; kernels.hip: the by-chunk rows table only moves the index loads; bwd_chain_mode only changes how the
+# sum a list in pieces; kernels_factor.hip: the by-chunk rows table only moves the index loads; kernels_solve.hip: bwd_chain_mode only changes how the
 # chain's workgroups wait for and publish x)
 BIT_IDENTICAL = [
     ("g2_1_plain", "acc1_plain"),
