@@ -49,7 +49,7 @@ struct ChainItem { int pn, need; };                                             
 // triangle -- 6 m <= 6 PANEL_MAX scalar columns -- behind as 16x16 tiles of 256 doubles in MFMA A-operand order (column-major), NTILE slots
 // per panel from PanelDesc::top on: first the NLT strictly-lower tiles (J, I), I < J, at slot J (J - 1) / 2 + I, NEGATED, then the NJMAX
 // diagonal tiles at slot NLT + J, INVERTED.  k_panel_rows* and the panel solves (k_fwd_tri, k_bwd_tri, k_bwd_fused, k_bwd_chain,
-// kernels_solve.hip) read them through the same numbers; fgo_structure.cpp sizes the buffer from them.
+// kernels_solve.hip) read them through the same numbers; structure_upload.cpp sizes the buffer from them.
 constexpr int NJMAX = (6 * PANEL_MAX + 15) / 16;       // 16-wide tile rows of a panel's dense scalar triangle
 constexpr int NLT = NJMAX * (NJMAX - 1) / 2;           // strictly-lower tiles
 constexpr int NTILE = NLT + NJMAX;                     // tile slots of a panel in ptop: the strictly-lower ones, then the diagonal ones
@@ -90,7 +90,7 @@ constexpr int EDGE_REC = 32;    // doubles per edge record (256 B = two 128-byte
 // ceil(degree / HUB_SLICE)) of them ("slices"), which stride through the variable's list TOGETHER -- thread t of slice q takes
 // the half-edges q * 256 + t, + 256 n, ... (513 half-edges: two slices, two evaluations on thread 0 of slice 0, one on every
 // other thread; a plane seen from 50 000 keyframes: 64 workgroups, 3 - 4 evaluations per thread) -- the slices' partial sums
-// combined in a fixed order by k_hub_combine*.  hub_deg is chosen per graph (fgo_structure.cpp plan_hubs): the smallest of
+// combined in a fixed order by k_hub_combine*.  hub_deg is chosen per graph (structure_grow.cpp plan_hubs): the smallest of
 // 64 .. 1024 that leaves at most HUB_MAX_VARS hub variables -- a few hundred planes seen from everywhere become hubs at
 // 64; the 10 000 cameras of a bundle adjustment (~500 observations each, plenty of them to fill the chip) stay on the
 // 4-lane path, which measured faster for them.
@@ -146,7 +146,7 @@ struct DevPlan {
   int64_t n_real;               // variables [n_real, n_poses) are unclaimed growth slots (identity diagonal, no update): n_poses when there are none
   int64_t edge_stride;          // capacity of the edge arrays in edges (>= n_edges: incremental mode keeps room for later factors)
   // 6-variable IMU factors: payload, variable ids, H slot of each of the 15 pairs.  This rank's factors are listed by COLOUR
-  // (two factors of one colour share no variable: fgo_structure.cpp imu_colour); a launch per colour adds every factor's
+  // (two factors of one colour share no variable: structure_grow.cpp imu_colour); a launch per colour adds every factor's
   // blocks straight into H, without atomics and in a fixed order.
   int64_t n_imu;
   const ImuPayload *imu;

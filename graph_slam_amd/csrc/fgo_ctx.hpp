@@ -239,7 +239,7 @@ struct fgo_ctx {
     size_t hub_cap = 0;                           // hub entries the scratch buffers (d_partial, d_hub_part) were sized for
     bool valid = false;
   } inc;
-  // IMU factors of this rank by colour (imu_colour_add / imu_colour_lists in fgo_structure.cpp): factors of one colour share no variable
+  // IMU factors of this rank by colour (imu_colour_add / imu_colour_lists in structure_grow.cpp): factors of one colour share no variable
   std::vector<uint64_t> imu_var_mask;           // [NX] colours 0 .. 63 taken at a variable
   std::vector<int> imu_flist, imu_fcolor;       // this rank's factors in input order, and their colours (>= 64: a colour of its own)
   std::vector<int> imu_color_ptr;               // [colours + 1] into the colour-sorted list on the device (d_imu_list)
@@ -293,7 +293,7 @@ void pose_inv7(const double *a, double *o);
 int upload_poses(fgo_ctx *c);
 int download_poses(fgo_ctx *c);
 int ensure_ready(fgo_ctx *c);
-// fgo_structure.cpp
+// fgo_structure.cpp / structure_grow.cpp
 int build(fgo_ctx *c);
 int refresh_factors(fgo_ctx *c);
 // fgo_dist.cpp

@@ -203,7 +203,7 @@ __global__ __launch_bounds__(SPLIT * 64) void k_chol_acc(DevPlan P, const double
     //  every XCD takes a CONTIGUOUS range of the long targets -- the targets of a column / panel share their sources)
     const int64_t ti = long0 + xcd_contiguous((int)blockIdx.x - n_acc_wg, n_long);      // (long0 = first + count in a full sweep)
     if (P.task_dirty && !P.task_dirty[P.acc_task[ti]]) return;
-    // (AccDesc, fgo_structure.cpp: riders have applied the head of the list -> continue from the value in L, or, for a hub target, from H: its
+    // (AccDesc, structure_upload.cpp: riders have applied the head of the list -> continue from the value in L, or, for a hub target, from H: its
     //  riders left their sums in scratch blocks that the rest of the list subtracts; a top block's value (incl. the domains' updates) sits in L)
     const AccDesc dsc = P.acc_desc[ti];
     const int64_t t = dsc.t;
@@ -457,7 +457,7 @@ __global__ __launch_bounds__(NW * 64) void k_chol_leaf(DevPlan P, const double *
   // on entry): once column k is final every lane knows L_kk, computes y_k and subtracts L_ik y_k from the rows i of its
   // own blocks -- column-oriented substitution with no extra barrier and no extra pass over L.
   extern __shared__ __attribute__((aligned(16))) double Ls[];
-  // one descriptor per task (fgo_structure.cpp "LeafDesc"): in a full sweep the level's tasks by descending work, in a partial sweep
+  // one descriptor per task (structure_upload.cpp "LeafDesc"): in a full sweep the level's tasks by descending work, in a partial sweep
   // (a task range) in task order
   const LeafDesc dsc = (P.task_dirty ? P.pp.leaf_desc : P.pp.leaf_lpt)[task0 + blockIdx.x];
   const int task = dsc.task;
@@ -1099,7 +1099,7 @@ __device__ __forceinline__ void panel_rows_body(const DevPlan &P, const double *
   const RowChunk rc = P.pp.rchunks[ci];
   const int lane = threadIdx.x, nn = lane & 15, q = lane >> 4;
   // BYC (narrow levels, 16-column panels): the source codes of this lane's scalar row from the table laid out by chunk -- addressed without the
-  // descriptor, so both requests travel together (fgo_structure.cpp "rchunk_src")
+  // descriptor, so both requests travel together (structure_upload.cpp "rchunk_src")
   int scq[4 * NJMAX];
   if constexpr (BYC) {
     const int *__restrict__ rsq = P.pp.rchunk_src + ((int64_t)(ci - P.pp.rchunk_src0) * 16 + nn) * PANEL_MAX;

@@ -1,4 +1,4 @@
-"""Graphs that grow IN PLACE (refresh_factors, fgo_structure.cpp) through the forms the linearisation can take afterwards: duplicate
+"""Graphs that grow IN PLACE (refresh_factors, structure_grow.cpp) through the forms the linearisation can take afterwards: duplicate
 groups forming and gaining members in either orientation, a variable crossing the hub threshold, a one-slice hub becoming a
 multi-slice hub, plane / point hubs, variables of every kind claiming phantom slots, priors arriving later, the masked ISAM2
 linearisation losing its precondition, and the hub buffers overflowing.
@@ -16,7 +16,7 @@ from tests.util import pose_mul, pose_inv, noisy, random_info, info_ut, quat_rot
 POSE, PLANE, POINT = 0, 1, 2                          # variable kinds (VK_*)
 SE3, BETWEEN, PLANEF, REPROJ = 0, 1, 2, 3             # factor kinds (FK_*)
 HUB_SLICE, HUB_MAX_SLICES, HUB_MAX_VARS, HUB_DEG_MAX = 512, 64, 1024, 1024      # device_plan.hpp
-HUB_CAP_EXTRA, EDGE_CAP_EXTRA = 256, 4096             # fgo_structure.cpp: hub entries / edges the growth reserve adds room for
+HUB_CAP_EXTRA, EDGE_CAP_EXTRA = 256, 4096             # structure_upload.cpp / structure_tables.cpp: hub entries / edges the growth reserve adds room for
 SOFT_PRIOR = info_ut(np.diag([1e6] * 6))              # as tests/test_gpu_isam2.py
 BPS = np.concatenate([[0.05, -0.02, 0.1], [0.5, 0.5, 0.5, 0.5]])     # body_P_sensor of tests.util.mixed_graph
 

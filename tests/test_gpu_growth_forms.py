@@ -1,4 +1,4 @@
-"""The linearised system after the structure has been extended IN PLACE (refresh_factors, fgo_structure.cpp), pinned at the H / b level.
+"""The linearised system after the structure has been extended IN PLACE (refresh_factors, structure_grow.cpp), pinned at the H / b level.
 
 Every case of tests/growth_forms.py grows a small graph step by step through one of the forms the extension has to get right -- a
 duplicate group forming or gaining a member in either orientation, a duplicate on a pair with a fixed end, a variable crossing the

@@ -61,7 +61,7 @@ def test_vio_linearization_matches_oracle(seed, planes):
 
 
 def test_imu_factors_sharing_one_bias_pair():
-    """Colouring of the IMU factors (fgo_structure.cpp imu_colour_add): every factor adds its blocks straight into H in the
+    """Colouring of the IMU factors (structure_grow.cpp imu_colour_add): every factor adds its blocks straight into H in the
     launch of its colour.  69 factors that all use the SAME two bias variables (a constant-bias model) conflict pairwise: the
     64 colours run out and the rest take a launch each.  H / b / chi2 against the oracle as above."""
     rng = np.random.default_rng(3)

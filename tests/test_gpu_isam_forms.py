@@ -176,7 +176,7 @@ PATTERNS = ["lo_after_first", "hi_before_last", "clean_inside", "riders_only", "
 # (set, pattern) that these graphs cannot reach, and why; checked both ways
 masked = "the masked sweep launches full grids: there are no ranges"
 PATTERN_EXCEPT = {("ranges_off", p): masked for p in ("lo_after_first", "hi_before_last", "clean_inside", "riders_only")}
-# (fgo_structure.cpp: a panel level's forward work items come from the table only where a row is split, i.e. has >= fwd_split = 32
+# (structure_upload.cpp: a panel level's forward work items come from the table only where a row is split, i.e. has >= fwd_split = 32
 #  chunks of external entries; no row of these graphs is that long, so the table is reached by the set that lowers fwd_split alone)
 PATTERN_EXCEPT.update({(s[0], "fwd_table"): "no row is long enough to be split at the default fwd_split" for s in FORM_SETS if s[0] != "fwd_split"})
 

@@ -1,4 +1,4 @@
-"""The host side of fgo_build (fgo_structure.cpp: pair records, block graph, edge slots, half-edge lists -- counted and placed
+"""The host side of fgo_build (structure_pairs.cpp, structure_tables.cpp: pair records, block graph, edge slots, half-edge lists -- counted and placed
 with atomic increments on all host threads, every list sorted afterwards) must hand the device the same tables whatever the
 thread count: same structure statistics, bit-identical LM trajectory and estimate.  FGO_HOST_THREADS is read once per process,
 hence the subprocesses."""
@@ -76,7 +76,7 @@ print("RESULT " + json.dumps([st.nnz_L_blocks, st.n_update_ops, st.n_levels, has
 
 
 def test_factor_does_not_depend_on_the_launch_order_of_the_triangle_kernels():
-    """PanelPlan::tri_order (fgo_structure.cpp): the throughput triangle kernels of a wide level take its panels in width order
+    """PanelPlan::tri_order (structure_upload.cpp): the throughput triangle kernels of a wide level take its panels in width order
     (narrowest first for one wave per panel, widest first for eight waves) -- a permutation of independent workgroups, so the
     factor, the LM trajectory and the estimate must be the same bit for bit as in task order (FGO_TUNE tri_lpt=0), and with the
     orders forced the other way round (2 / 3).  60 000 poses: levels of > 3 x 256 panels (k_panel_tri1) and of > 256 (k_panel_tri<8>)."""
