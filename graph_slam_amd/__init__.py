@@ -147,6 +147,23 @@ class PlanePropagatePred(C.Structure):
 
 FGO_PP_OK, FGO_PP_NUM = 0, 2
 
+
+class MatchParams(C.Structure):
+    """fgo_match_params"""
+    _fields_ = [("ratio", C.c_double), ("ratio_test", C.c_int), ("cross_check", C.c_int), ("max_desc_dist2", C.c_int32),
+                ("min_matches", C.c_int), ("radius_px", C.c_double), ("max_dist_3d", C.c_double), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double)]
+
+
+class MatchResult(C.Structure):
+    """fgo_match_result"""
+    _fields_ = [("status", C.c_int), ("n_query", C.c_int), ("n_train", C.c_int), ("n_matches", C.c_int), ("n_ratio", C.c_int),
+                ("n_cross", C.c_int)]
+
+
+FGO_FM_OK, FGO_FM_TOO_FEW = 0, 1
+FGO_FM_DIM, FGO_FM_MAX_FEATURES = 128, 4096
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)     # fgo_allreduce_fn
 
 
@@ -267,6 +284,13 @@ def _load():
                                               C.POINTER(PlanePropagatePlane), C.POINTER(PlanePropagatePred), C.POINTER(C.c_int8)]
     lib.fgo_debug_plane_propagate_kernel_ms.restype = C.c_double
     lib.fgo_debug_plane_propagate_kernel_ms.argtypes = []
+    lib.fgo_match_params_default.restype = None
+    lib.fgo_match_params_default.argtypes = [C.POINTER(MatchParams)]
+    i32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+    lib.fgo_match_features_batch.argtypes = [C.c_int, C.c_int64, i64p, u8p, dp, dp, C.c_int64, i64p, i64p, dp, u8p, C.POINTER(MatchParams),
+                                             C.POINTER(MatchResult), i64p, i32p, i32p, i32p, u8p, i64p, i64p, i64p, dp, dp, dp, dp, i32p]
+    lib.fgo_debug_match_kernel_ms.restype = C.c_double
+    lib.fgo_debug_match_kernel_ms.argtypes = []
     lib.fgo_add_vec3.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_bias.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_prior_vec3.argtypes = [C.c_void_p, C.c_int64, dp, C.c_double]
@@ -710,6 +734,103 @@ def plane_node_batch(depth, intensity, labels, n_planes, abcd, cov16, frame_i, f
         keep = np.arange(MP)[None, :] < out["n_planes"][:, None]
         out["ptr"] = np.concatenate([[0], np.cumsum(out["n_planes"])]).astype(np.int64)
         out["abcd"] = out["abcd_all"][keep]; out["cov16"] = out["cov16_all"][keep].reshape(-1, 16); out["cov_ut6"] = out["cov_ut6_all"][keep]
+    return out
+
+
+def match_params(**kw):
+    """fgo_match_params_default, with the given fields replaced"""
+    p = MatchParams()
+    lib.fgo_match_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(MatchParams._fields_):
+            raise TypeError("fgo_match_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def match_features_batch(feat_ptr, desc, xyz, uv, frame_i, frame_j, pose_ij=None, guided=None, params=None, want_dist=False, device=0):
+    """fgo_match_features_batch: the descriptor matches of every pair of frames in one launch, one workgroup per pair.  Frame f owns
+    the features [feat_ptr[f], feat_ptr[f + 1]) of desc (F x 128 uint8), xyz (F x 3, camera frame) and uv (F x 2); pair p matches the
+    features of frame_j[p] (queries) against those of frame_i[p] (trains).  pose_ij (n_pairs x 7, p_i = R p_j + t: vro_ransac_batch's
+    pose_ij) guides every pair, or the pairs `guided` (n_pairs, bool) names.  Returns a dict of arrays.  Packed, as vro_ransac_batch and
+    two_view_ba_batch take them: ptr (n_pairs + 1), idx_i, idx_j (global feature indices), xyz_i, xyz_j (M x 3), uv_i, uv_j (M x 2).
+    Per query, indexed q_ptr[p] + a: best (the train's local index, -1 without a candidate), d1, d2 (-1: none), reason (0 kept, 1 not
+    usable, 2 no candidate, 3 ratio test, 4 absolute cap, 5 cross-check).  Over the pairs: status (FGO_FM_*), n_query, n_train,
+    n_matches, n_ratio, n_cross.  With want_dist, dist: the N_j x N_i matrix of every pair (int32, -1 where (a, b) is no candidate),
+    one after the other."""
+    fp = np.ascontiguousarray(feat_ptr, np.int64).reshape(-1)
+    nf = len(fp) - 1
+    if nf < 0:
+        raise FgoError("match_features_batch: feat_ptr needs n_frames + 1 entries")
+    F = max(int(fp[-1]), 0)
+    d = np.ascontiguousarray(desc, np.uint8).reshape(-1, FGO_FM_DIM)
+    x = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3); u = np.ascontiguousarray(uv, np.float64).reshape(-1, 2)
+    if min(len(d), len(x), len(u)) < F:
+        raise FgoError("match_features_batch: feat_ptr names %d features, the arrays hold fewer" % F)
+    fi = np.ascontiguousarray(frame_i, np.int64).reshape(-1); fj = np.ascontiguousarray(frame_j, np.int64).reshape(-1)
+    n = len(fi)
+    if len(fj) != n:
+        raise FgoError("match_features_batch: frame_i and frame_j need one entry per pair")
+    ps = None if pose_ij is None else np.ascontiguousarray(pose_ij, np.float64).reshape(-1, 7)
+    gd = None if guided is None else np.ascontiguousarray(np.asarray(guided) != 0, np.uint8).reshape(-1)
+    if (ps is not None and len(ps) != n) or (gd is not None and len(gd) != n):
+        raise FgoError("match_features_batch: pose_ij and guided need one entry per pair")
+    if params is None:
+        params = match_params()
+    ok = (np.diff(fp) >= 0).all() and fp[0] >= 0 and ((fi >= 0) & (fi < nf) & (fj >= 0) & (fj < nf)).all()
+    cnt = np.diff(fp)
+    nq = cnt[fj] if ok else np.zeros(n, np.int64)               # a bad argument is the library's to refuse
+    Q = int(nq.sum()); T = int((nq * cnt[fi]).sum()) if ok else 0
+    q_ptr = np.zeros(n + 1, np.int64); ptr = np.zeros(n + 1, np.int64)
+    best = np.zeros(Q, np.int32); d1 = np.zeros(Q, np.int32); d2 = np.zeros(Q, np.int32); why = np.zeros(Q, np.uint8)
+    idx_i = np.zeros(Q, np.int64); idx_j = np.zeros(Q, np.int64)
+    xi = np.zeros((Q, 3)); xj = np.zeros((Q, 3)); ui = np.zeros((Q, 2)); uj = np.zeros((Q, 2))
+    dist = np.zeros(T, np.int32) if want_dist else None
+    res = (MatchResult * max(n, 1))()
+    i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    u8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))
+    rc = lib.fgo_match_features_batch(device, nf, _i64p(fp), u8(d), _dp(x), _dp(u), n, _i64p(fi), _i64p(fj),
+                                      None if ps is None else _dp(ps), None if gd is None else u8(gd), C.byref(params), res, _i64p(q_ptr),
+                                      i32(best), i32(d1), i32(d2), u8(why), _i64p(ptr), _i64p(idx_i), _i64p(idx_j), _dp(xi), _dp(xj),
+                                      _dp(ui), _dp(uj), None if dist is None else i32(dist))
+    if rc < 0:
+        raise FgoError("fgo_match_features_batch failed: %d" % rc)
+    fields = ("status", "n_query", "n_train", "n_matches", "n_ratio", "n_cross")
+    r = np.frombuffer(res, dtype=np.dtype([(f, "i4") for f in fields]), count=n)
+    out = {k: r[k].copy() for k in fields}
+    m = int(ptr[-1])
+    out.update(ptr=ptr, idx_i=idx_i[:m], idx_j=idx_j[:m], xyz_i=xi[:m], xyz_j=xj[:m], uv_i=ui[:m], uv_j=uj[:m], q_ptr=q_ptr, best=best,
+               d1=d1, d2=d2, reason=why)
+    if dist is not None:
+        out["dist"] = dist
+    return out
+
+
+def vro_adjust_batch(feat_ptr, desc, xyz, uv, frame_i, frame_j, pose_ij, info=None, params=None, ransac_params=None, min_matches=5,
+                     device=0):
+    """CGraphGT::vroAdjust (gtsam/gtsam_graph.cpp:450-498) for every record, by composition: the guided match of the pair under the
+    record's pose (matchNodePairBA(ni, Tji, pcam): match_features_batch with pose_ij), then vro_ransac_batch on those matches (the
+    reference's getTransformFromMatches on them).  A record with fewer than min_matches matches (5: matches.size() <= 4, :463), or
+    whose registration fails, is left as it is.  Returns a dict: adjusted (n_pairs, bool), pose_ij (n_pairs x 7) and info
+    (n_pairs x 21; the rows of the records left alone are the caller's, zeros where info was not given), n_matches, and the two
+    calls' own dicts `match` and `vro` (vro covers the pairs in `tried`, None when there was none)."""
+    ps = np.ascontiguousarray(pose_ij, np.float64).reshape(-1, 7)
+    n = len(ps)
+    m = match_features_batch(feat_ptr, desc, xyz, uv, frame_i, frame_j, pose_ij=ps, params=params, device=device)
+    pose = ps.copy()
+    nf = np.zeros((n, 21)) if info is None else np.array(info, np.float64).reshape(n, 21)
+    adjusted = np.zeros(n, bool)
+    tried = np.nonzero(m["n_matches"] >= min_matches)[0]
+    out = dict(match=m, vro=None, tried=tried, n_matches=m["n_matches"].copy())
+    if len(tried):
+        sel = np.concatenate([np.arange(m["ptr"][p], m["ptr"][p + 1]) for p in tried]).astype(np.int64)
+        sp = np.concatenate([[0], np.cumsum(m["n_matches"][tried])]).astype(np.int64)
+        v = vro_ransac_batch(sp, m["xyz_i"][sel], m["xyz_j"][sel], params=ransac_params, device=device, want_cov=False, want_inliers=False)
+        good = v["status"] == FGO_VRO_OK
+        pose[tried[good]] = v["pose_ij"][good]; nf[tried[good]] = v["info"][good]
+        adjusted[tried[good]] = True
+        out["vro"] = v
+    out.update(adjusted=adjusted, pose_ij=pose, info=nf)
     return out
 
 

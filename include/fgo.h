@@ -545,6 +545,75 @@ int fgo_vro_ransac_batch(int device, int64_t n_pairs, const int64_t *match_ptr /
 int fgo_debug_vro_waves(int waves);
 double fgo_debug_vro_kernel_ms(void);
 
+/* Descriptor matching of key-frame pairs, batched: the step that PRODUCES the matched 3-D features the calls above start from --
+ * CCameraNode::matchNodePair before its RANSAC (g2o/g2o_graph.cpp:174,210-211, gtsam/gtsam_graph.cpp:1730-1731) and the pose-guided
+ * matchNodePairBA(ni, Tji, pcam) of CGraphGT::vroAdjust (gtsam/gtsam_graph.cpp:450-498, gtsam/test/convert_vo2ba.cpp:206) -- for
+ * n_pairs independent pairs in ONE launch, one workgroup per pair.  The reference fixes 128-byte SIFT descriptors, m_nn_distance_ratio
+ * = 0.5 and m_min_matches = 12 (gtsam/test_gt_graph.cpp:165-172); the matching arithmetic itself (matchNodePair, matchNodePairBA,
+ * the FLANN search) is not part of the reference tree, so the semantics below are THIS PROJECT'S DEFINITION, pinned to the numpy
+ * restatement tests/feature_match_reference.py and not to the VRO library.
+ * Frame f owns the features [feat_ptr[f], feat_ptr[f+1]) of desc (SIFT as OpenCV stores it, integers 0 .. 255), xyz (camera frame)
+ * and uv (undistorted pixels).  Pair p matches the features of frame_j[p] (the queries, local index a) against those of frame_i[p]
+ * (the trains, local index b).  pose_ij7 (t q_xyzw, p_i = R p_j + t, as fgo_vro_ransac_batch writes it) guides a pair: NULL = no
+ * pair is guided; with guided == NULL every pair is, otherwise the pairs with guided[p] != 0.
+ *   usable      a feature whose three coordinates are finite with z > 0; any other never matches (reason 1) and is no candidate.
+ *   distance    d(a, b) = sum_k (desc_a[k] - desc_b[k])^2, an integer <= 128 * 255^2 = 8 323 200, computed exactly.
+ *   candidates  unguided: every usable (a, b).  Guided: also gate(a, b): with p = R^T (xyz_b - t), the train in frame j, p.z > 0 and
+ *               (fx p.x / p.z + cx - u_a)^2 + (fy p.y / p.z + cy - v_a)^2 <= radius_px^2 and, if max_dist_3d > 0,
+ *               |p - xyz_a|^2 <= max_dist_3d^2.  The gate belongs to the PAIR (a, b): the cross-check runs over the same set.
+ *   best        b1 = the candidate with the smallest d, ties to the lowest b; d1 = d(a, b1); d2 = the smallest d over the
+ *               candidates other than b1 (a tie at the minimum gives d2 = d1).  No candidate: reason 2, best = d1 = d2 = -1.
+ *               Exactly one candidate: d2 = -1 and the ratio test passes.
+ *   ratio       (if ratio_test) kept iff (double) d1 < r2 * (double) d2 with r2 = ratio * ratio formed once in f64; else reason 3.
+ *   cap         d1 <= max_desc_dist2, else reason 4.
+ *   cross       (if cross_check) kept iff a is the candidate query with the smallest d(., b1), ties to the lowest a; else reason 5.
+ *               Without it several queries may keep the same train.
+ * The first test that fails gives the reason; reason 0 is a match.  The matches of a pair are its kept queries in ascending a.
+ * Per query, indexed q_ptr[p] + a with q_ptr the prefix sum of the pairs' query counts (Q = q_ptr[n_pairs]): best_out (b1), d1_out,
+ * d2_out, reason_out.  Packed by the host after the download, capacity Q rows, the first match_ptr_out[n_pairs] filled:
+ * idx_i_out / idx_j_out (GLOBAL feature indices) and the gathers xyz_i_out, xyz_j_out, uv_i_out, uv_j_out -- with match_ptr_out
+ * exactly what fgo_vro_ransac_batch and fgo_two_view_ba_batch take.  dist_out (for tests and diagnosis, like hyp_count_out): the
+ * full matrix of every pair one after the other, N_j x N_i int32, row a, column b, -1 where (a, b) is no candidate.
+ * result: n_query / n_train = the usable features of frame j / frame i, n_matches, n_ratio / n_cross = the queries the ratio test /
+ * the cross-check rejected (reasons 3 / 5); status FGO_FM_TOO_FEW when n_matches < min_matches -- the matches are written all the
+ * same, the caller applies the reference's 4 (gtsam_graph.cpp:463) / 8 / 20 (convert_vo2ba.cpp:210,231) thresholds itself.
+ * The arithmetic is integer, the column minima are integer atomic minima: results are bit-identical from call to call and a pair's
+ * result does not depend on the rest of the batch.  Stateless, host arrays in and out, like fgo_vro_ransac_batch.  FGO_EINVAL
+ * (before any HIP call): a NULL required pointer, a negative n_frames or n_pairs, a negative or decreasing feat_ptr, more than
+ * FGO_FM_MAX_FEATURES features in a frame, a frame index outside [0, n_frames), a zero quaternion on a guided pair, ratio outside
+ * (0, 1], radius_px / fx / fy <= 0, max_dist_3d < 0, max_desc_dist2 < 0, min_matches < 0; FGO_ENODEV without a HIP device (no CPU
+ * fallback).  n_pairs == 0: FGO_OK. */
+#define FGO_FM_DIM 128
+#define FGO_FM_MAX_FEATURES 4096
+typedef struct {
+  double ratio;          /* 0.5  m_nn_distance_ratio (test_gt_graph.cpp:165-172); compared squared, on squared distances */
+  int ratio_test;        /* 1 */
+  int cross_check;       /* 1 */
+  int32_t max_desc_dist2;/* INT32_MAX: off */
+  int min_matches;       /* 12  m_min_matches */
+  double radius_px;      /* 10.0 (our choice) */
+  double max_dist_3d;    /* 0: off */
+  double fx, fy, cx, cy; /* 250.5773, 250.5773, 90, 70: the SR4000 pinhole */
+} fgo_match_params;
+void fgo_match_params_default(fgo_match_params *p);        /* NULL tolerated */
+#define FGO_FM_OK 0
+#define FGO_FM_TOO_FEW 1    /* n_matches < min_matches */
+typedef struct { int status, n_query, n_train, n_matches, n_ratio, n_cross; } fgo_match_result;
+int fgo_match_features_batch(int device, int64_t n_frames, const int64_t *feat_ptr /* n_frames + 1 */,
+                             const uint8_t *desc /* F x 128 */, const double *xyz /* F x 3 */, const double *uv /* F x 2 */,
+                             int64_t n_pairs, const int64_t *frame_i, const int64_t *frame_j,
+                             const double *pose_ij7 /* n x 7, or NULL */, const uint8_t *guided /* n, or NULL */,
+                             const fgo_match_params *params /* NULL = defaults */,
+                             fgo_match_result *result /* n */, int64_t *q_ptr_out /* n + 1, may be NULL */,
+                             int32_t *best_out /* Q, may be NULL */, int32_t *d1_out /* Q, may be NULL */,
+                             int32_t *d2_out /* Q, may be NULL */, uint8_t *reason_out /* Q, may be NULL */,
+                             int64_t *match_ptr_out /* n + 1 */, int64_t *idx_i_out /* Q */, int64_t *idx_j_out /* Q */,
+                             double *xyz_i_out /* Q x 3, may be NULL */, double *xyz_j_out /* Q x 3, may be NULL */,
+                             double *uv_i_out /* Q x 2, may be NULL */, double *uv_j_out /* Q x 2, may be NULL */,
+                             int32_t *dist_out /* sum N_j N_i, may be NULL: for tests and diagnosis */);
+/* development: the kernel time of the last fgo_match_features_batch call by HIP events, ms */
+double fgo_debug_match_kernel_ms(void);
+
 /* LevenbergMarquardtOptimizer(graph, values).optimize() with GTSAM 4.0's default parameters —
  *      CGraphGT::optimizeGraphBatch, gtsam/gtsam_graph.cpp:1784-1788.  max_iters <= 0 selects the default 100.
  *      Returns the number of iterations performed or a negative code. */
