@@ -164,6 +164,22 @@ class MatchResult(C.Structure):
 FGO_FM_OK, FGO_FM_TOO_FEW = 0, 1
 FGO_FM_DIM, FGO_FM_MAX_FEATURES = 128, 4096
 
+
+class MapParams(C.Structure):
+    """fgo_map_params"""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("z_scale", C.c_double),
+                ("z_min", C.c_double), ("z_max", C.c_double), ("skip", C.c_int), ("rect", C.c_int * 4), ("leaf", C.c_double),
+                ("min_points", C.c_int), ("table_log2", C.c_int)]
+
+
+class MapResult(C.Structure):
+    """fgo_map_result"""
+    _fields_ = [("status", C.c_int), ("table_log2", C.c_int), ("n_sampled", C.c_int64), ("n_valid", C.c_int64),
+                ("n_out_of_range", C.c_int64), ("n_voxels", C.c_int64), ("n_dropped", C.c_int64)]
+
+
+FGO_MAP_OK, FGO_MAP_TRUNCATED, FGO_MAP_FULL = 0, 1, 2
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)     # fgo_allreduce_fn
 
 
@@ -291,6 +307,12 @@ def _load():
                                              C.POINTER(MatchResult), i64p, i32p, i32p, i32p, u8p, i64p, i64p, i64p, dp, dp, dp, dp, i32p]
     lib.fgo_debug_match_kernel_ms.restype = C.c_double
     lib.fgo_debug_match_kernel_ms.argtypes = []
+    lib.fgo_map_params_default.restype = None
+    lib.fgo_map_params_default.argtypes = [C.POINTER(MapParams)]
+    lib.fgo_map_fuse_batch.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_uint16), u8p, C.c_int, dp, dp, C.POINTER(MapParams),
+                                       C.c_int64, C.POINTER(MapResult), dp, u8p, C.POINTER(C.c_int32), i64p, i64p, dp]
+    lib.fgo_debug_map_fuse_kernel_ms.restype = C.c_double
+    lib.fgo_debug_map_fuse_kernel_ms.argtypes = []
     lib.fgo_add_vec3.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_bias.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_prior_vec3.argtypes = [C.c_void_p, C.c_int64, dp, C.c_double]
@@ -832,6 +854,91 @@ def vro_adjust_batch(feat_ptr, desc, xyz, uv, frame_i, frame_j, pose_ij, info=No
         out["vro"] = v
     out.update(adjusted=adjusted, pose_ij=pose, info=nf)
     return out
+
+
+def map_params(**kw):
+    """fgo_map_params_default, with the given fields replaced (rect: su, sv, eu, ev)"""
+    p = MapParams()
+    lib.fgo_map_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(MapParams._fields_):
+            raise TypeError("fgo_map_params has no field %r" % k)
+        setattr(p, k, (C.c_int * 4)(*v) if k == "rect" else v)
+    return p
+
+
+def map_fuse_batch(depth, pose_w, color=None, extrinsic=None, params=None, max_voxels=None, want_keys=False, want_rt=False, device=0):
+    """fgo_map_fuse_batch: the voxel-grid map of all depth frames in one call.  depth is n x H x W (or H x W for one frame) of uint16
+    depth words, pose_w n x 7 (t, q_xyzw: Graph.get_poses), color None, n x H x W (grey) or n x H x W x 3 (uint8), extrinsic the 7
+    numbers of Pu2c or None.  max_voxels defaults to the bound n_sampled.  Returns a dict: xyz (m x 3), color (m x channels, None
+    without colour), count (m, int32), frame_points (n, int64), with want_keys key (m, int64) and with want_rt rt (n x 12), each
+    trimmed to m = min(n_voxels, max_voxels), in ascending key; and the result fields status (FGO_MAP_*), table_log2, n_sampled,
+    n_valid, n_out_of_range, n_voxels, n_dropped."""
+    d = np.ascontiguousarray(depth, np.uint16)
+    if d.ndim == 2:
+        d = d[None]
+    if d.ndim != 3:
+        raise FgoError("map_fuse_batch: depth is n x H x W")
+    n, h, w = d.shape
+    ps = np.ascontiguousarray(pose_w, np.float64).reshape(-1, 7)
+    if len(ps) != n:
+        raise FgoError("map_fuse_batch: pose_w needs one row of 7 per frame")
+    col, ch = None, 0
+    if color is not None:
+        col = np.ascontiguousarray(color, np.uint8)
+        if col.shape == (h, w) or col.shape == (h, w, 3):
+            col = col[None]
+        if col.shape not in ((n, h, w), (n, h, w, 1), (n, h, w, 3)):
+            raise FgoError("map_fuse_batch: color is n x H x W or n x H x W x 3")
+        ch = 3 if col.shape[-1] == 3 and col.ndim == 4 else 1
+    ext = None if extrinsic is None else np.ascontiguousarray(extrinsic, np.float64).reshape(7)
+    if params is None:
+        params = map_params()
+    if max_voxels is None:                                        # the bound n_sampled; a bad argument is the library's to refuse
+        su, sv, eu, ev = params.rect
+        if (su, sv, eu, ev) == (0, 0, 0, 0):
+            eu, ev = w, h
+        k = max(params.skip, 1)
+        max_voxels = n * max(-(-(eu - su) // k), 0) * max(-(-(ev - sv) // k), 0)
+    cap = max(int(max_voxels), 0)
+    xyz = np.zeros((cap, 3)); cout = np.zeros((cap, ch), np.uint8) if ch else None
+    cnt = np.zeros(cap, np.int32); key = np.zeros(cap, np.int64) if want_keys else None
+    fpts = np.zeros(n, np.int64); rt = np.zeros((n, 12)) if want_rt else None
+    res = MapResult()
+    u8 = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8))
+    rc = lib.fgo_map_fuse_batch(device, n, w, h, d.ctypes.data_as(C.POINTER(C.c_uint16)), u8(col), ch, _dp(ps), None if ext is None else _dp(ext),
+                                C.byref(params), int(max_voxels), C.byref(res), _dp(xyz), u8(cout), cnt.ctypes.data_as(C.POINTER(C.c_int32)),
+                                None if key is None else _i64p(key), _i64p(fpts), None if rt is None else _dp(rt))
+    if rc < 0:
+        raise FgoError("fgo_map_fuse_batch failed: %d" % rc)
+    out = {f: int(getattr(res, f)) for f, _ in MapResult._fields_}
+    m = 0 if res.status == FGO_MAP_FULL else min(res.n_voxels, cap)
+    out.update(xyz=xyz[:m], color=None if cout is None else cout[:m], count=cnt[:m], frame_points=fpts)
+    if key is not None:
+        out["key"] = key[:m]
+    if rt is not None:
+        out["rt"] = rt
+    return out
+
+
+def write_ply(path, xyz, color=None):
+    """an ASCII PLY in the layout of the reference's headerPLY (mapping/mapping_PCD.cpp:169-181): float x y z, uchar red green blue.
+    color is m x 3, m or m x 1 (grey, repeated three times) or None (255)."""
+    xyz = np.asarray(xyz, np.float64).reshape(-1, 3)
+    m = len(xyz)
+    if color is None:
+        rgb = np.full((m, 3), 255, np.uint8)
+    else:
+        rgb = np.asarray(color, np.uint8).reshape(m, -1)
+        if rgb.shape[1] == 1:
+            rgb = np.repeat(rgb, 3, 1)
+        if rgb.shape[1] != 3:
+            raise FgoError("write_ply: color is m x 3 or m")
+    with open(path, "w") as f:
+        f.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % m)
+        for p, c in zip(xyz, rgb):
+            f.write("%.9g %.9g %.9g %d %d %d\n" % (p[0], p[1], p[2], c[0], c[1], c[2]))
 
 
 def synth_manhattan3d(n_poses, lookback=5, n_loop=4, seed=42, sigma_t=0.02, sigma_q=0.005):

@@ -614,6 +614,78 @@ int fgo_match_features_batch(int device, int64_t n_frames, const int64_t *feat_p
 /* development: the kernel time of the last fgo_match_features_batch call by HIP events, ms */
 double fgo_debug_match_kernel_ms(void);
 
+/* Voxel-grid map fusion of depth frames, batched: the step that turns the optimised trajectory into the run's product, the map --
+ * mapping/mapping_PCD.cpp:86-167, mapping_PCD_rs.cpp:127-252, mapping_PLY*.cpp, map_video*.cpp: every key frame is back-projected
+ * (generatePointCloud), range-filtered (passThroughZ), carried into the world by Pw2c = Pw2j * Pu2c (mapping_PCD.cpp:140-144),
+ * appended to the map and thinned with pcl::VoxelGrid at voxel_grid_size = 0.02 (mapping_PCD_rs.cpp:59-66,220-229), frame after frame
+ * on the CPU -- for ALL n_frames in ONE call.  PCL is not part of the reference tree, so the semantics below are THIS PROJECT'S
+ * DEFINITION, pinned to the numpy restatement tests/map_fuse_reference.py.  Where they differ from the reference: its grid is aligned
+ * to the cloud's bounding box and its arithmetic is in float, ours is world-aligned (voxel i covers [i, i + 1) leaves from the
+ * world's origin) with integer sums; it re-filters the accumulated map after each frame (an unweighted centroid of centroids), ours
+ * is ONE centroid per voxel over all points of all frames; lens distortion, the median filter of mapping_PLY_rs.cpp:172 and the
+ * clustering of pcd_filter.cpp are out of scope (min_points stands in for the last); the caller chooses the frames (trajectory_skip).
+ *   pose        frame f has pose_w7[f] = t_w(3) q_xyzw(4), as fgo_get_poses gives it; extrinsic7 (t_e, q_e) is Pu2c, NULL = identity.
+ *               A quaternion is normalised on entry: each component divided by sqrt(((qx qx + qy qy) + qz qz) + qw qw).  With the
+ *               normalised (x, y, z, w):  R00 = 1 - 2 (y y + z z)  R01 = 2 (x y - z w)      R02 = 2 (x z + y w)
+ *                                         R10 = 2 (x y + z w)      R11 = 1 - 2 (x x + z z)  R12 = 2 (y z - x w)
+ *                                         R20 = 2 (x z - y w)      R21 = 2 (y z + x w)      R22 = 1 - 2 (x x + y y)
+ *               each product and sum rounded on its own.  With an extrinsic R = R_w R_e, R_ij = (Rw_i0 Re_0j + Rw_i1 Re_1j) + Rw_i2 Re_2j,
+ *               and t_i = ((Rw_i0 te_0 + Rw_i1 te_1) + Rw_i2 te_2) + tw_i.  This runs on the host, without fused multiply-adds;
+ *               rt_out[f] = R row-major, then t: exactly what the kernel used.
+ *   sampling    the pixels (u, v) = (su + a skip, sv + b skip), a, b >= 0, u < eu, v < ev; rect = {su, sv, eu, ev}, all zero = the whole
+ *               image.  n_sampled counts them over all frames.
+ *   point       z = w z_scale for the depth word w; the point is valid iff z_min < z < z_max (the project's rule, not PCL's closed
+ *               interval).  p = (((u - cx) z) / fx, ((v - cy) z) / fy, z); x_k = ((R_k0 p_0 + R_k1 p_1) + R_k2 p_2) + t_k.  EVERY
+ *               product, quotient and sum is rounded to double on its own: the kernel does not contract them.
+ *   quantum     Q_k = llrint(x_k 2^20), ties to even: the quantum is 2^-20 m = 0.95 um.  L = llrint(leaf 2^20): the EFFECTIVE leaf is
+ *               L 2^-20 (0.02 m -> 20972 quanta = 0.0200005 m).  i_k = floor(Q_k / L), floor division of the QUANTISED coordinate: a
+ *               point at -1e-6 has Q = -1 and is in voxel -1, a point at -1e-7 rounds to Q = 0 and is in voxel 0.  r_k = Q_k - i_k L
+ *               lies in [0, L).  A valid point with a non-finite x_k or some |i_k| >= 2^20 is OUT OF RANGE: counted in
+ *               n_out_of_range, not in n_valid, not stored.
+ *   key         ((i_z + 2^20) << 42) | ((i_y + 2^20) << 21) | (i_x + 2^20)
+ *   voxel       n = its number of points, S_k = sum r_k, C_c = sum colour_c: integer sums, whatever the order of arrival.
+ *   output      the voxels with n >= min_points in ascending key (the others are counted in n_dropped):
+ *               xyz_k = ((double)(i_k L) + (double)S_k / (double)n) 2^-20, colour_c = (2 C_c + n) / (2 n) in integer division (the mean
+ *               rounded half up), count = n, key.  frame_points_out[f] = the valid points of frame f; n_valid their sum.
+ * result: status FGO_MAP_OK; FGO_MAP_TRUNCATED when n_voxels > max_voxels: n_voxels is the true number and the first max_voxels rows
+ * in key order are written; FGO_MAP_FULL when the hash table filled up: no voxel is written, n_voxels = n_dropped = 0 (the counts of
+ * points, frame_points_out and rt_out are written), and the call still returns FGO_OK.  table_log2 = T, the table has 2^T slots of
+ * 64 bytes: automatic (0) is the smallest T >= 4 with 2^T >= 2 n_sampled, which cannot fill; a caller who knows the map is small
+ * sets it lower.  Two calls give bit-identical outputs, and so does any permutation of the frames (frame_points_out and rt_out
+ * permuted alike).  Stateless, host arrays in and out, like fgo_plane_extract_batch; only min(n_voxels, max_voxels) rows are copied
+ * back.  FGO_EINVAL (before any HIP call): result NULL, n_frames < 0, max_voxels < 0, width or height < 1 or their product > 2^24,
+ * n_frames x sampled pixels >= 2^31, channels not 0, 1 or 3, fx, fy, z_scale <= 0 or not finite, cx or cy not finite,
+ * z_min >= z_max, skip < 1, a rect that is empty or not inside the image, leaf outside [2^-20, 1024], min_points < 1, table_log2
+ * outside {0} u [4, 32]; and for n_frames > 0: depth or
+ * pose_w7 NULL, xyz_out NULL with max_voxels > 0, color NULL with channels > 0 or not NULL with channels == 0, a zero (or
+ * non-finite) quaternion.  n_frames == 0: FGO_OK and a zero result.  FGO_ENODEV without a HIP device (no CPU fallback).  FGO_ENOMEM:
+ * the table does not fit: split the batch or set table_log2. */
+typedef struct {
+  double fx, fy, cx, cy;   /* 250.5773, 250.5773, 90, 70: the SR4000 pinhole */
+  double z_scale;          /* 0.001 */
+  double z_min, z_max;     /* 0.1, 5.0 (mapping_PCD_rs keeps 0 .. 1.2) */
+  int skip;                /* 2: downsample_skip, >= 1 */
+  int rect[4];             /* su, sv, eu, ev; all zero = the whole image; eu, ev exclusive */
+  double leaf;             /* 0.02 m: voxel_grid_size */
+  int min_points;          /* 1 */
+  int table_log2;          /* 0 = automatic; else in [4, 32] */
+} fgo_map_params;
+void fgo_map_params_default(fgo_map_params *p);            /* NULL tolerated */
+#define FGO_MAP_OK 0
+#define FGO_MAP_TRUNCATED 1  /* n_voxels > max_voxels: the first max_voxels in key order are written */
+#define FGO_MAP_FULL 2       /* the hash table is full: no outputs, n_voxels = 0 */
+typedef struct { int status, table_log2; int64_t n_sampled, n_valid, n_out_of_range, n_voxels, n_dropped; } fgo_map_result;
+int fgo_map_fuse_batch(int device, int64_t n_frames, int width, int height,
+                       const uint16_t *depth /* n x H x W */, const uint8_t *color /* n x H x W x channels, NULL iff channels == 0 */,
+                       int channels /* 0, 1 or 3 */, const double *pose_w7 /* n x 7: t(3) q_xyzw(4), as fgo_get_poses gives them */,
+                       const double *extrinsic7 /* Pu2c, NULL = identity */, const fgo_map_params *params /* NULL = defaults */,
+                       int64_t max_voxels, fgo_map_result *result /* 1 */,
+                       double *xyz_out /* max_voxels x 3 */, uint8_t *color_out /* max_voxels x channels, may be NULL */,
+                       int32_t *count_out /* may be NULL */, int64_t *key_out /* may be NULL */,
+                       int64_t *frame_points_out /* n, may be NULL */, double *rt_out /* n x 12, may be NULL */);
+/* development: the device time of the last fgo_map_fuse_batch call by HIP events (table init, insert, pack; sort, finalise), ms */
+double fgo_debug_map_fuse_kernel_ms(void);
+
 /* LevenbergMarquardtOptimizer(graph, values).optimize() with GTSAM 4.0's default parameters —
  *      CGraphGT::optimizeGraphBatch, gtsam/gtsam_graph.cpp:1784-1788.  max_iters <= 0 selects the default 100.
  *      Returns the number of iterations performed or a negative code. */
