@@ -180,6 +180,21 @@ class MapResult(C.Structure):
 
 FGO_MAP_OK, FGO_MAP_TRUNCATED, FGO_MAP_FULL = 0, 1, 2
 
+
+class MapCleanParams(C.Structure):
+    """fgo_map_clean_params"""
+    _fields_ = [("tolerance", C.c_double), ("min_cluster_size", C.c_int), ("max_cluster_size", C.c_int), ("remove_floor", C.c_int),
+                ("up_axis", C.c_int), ("up_sign", C.c_int), ("floor_res", C.c_double), ("floor_span", C.c_double),
+                ("floor_clearance", C.c_double)]
+
+
+class MapCleanResult(C.Structure):
+    """fgo_map_clean_result"""
+    _fields_ = [("n_points", C.c_int64), ("n_out_of_range", C.c_int64), ("n_cells", C.c_int64), ("n_clusters", C.c_int64),
+                ("n_clusters_kept", C.c_int64), ("n_after_clusters", C.c_int64), ("n_floor_removed", C.c_int64), ("n_kept", C.c_int64),
+                ("floor_bin", C.c_int64), ("floor_bin_points", C.c_int64), ("floor_height", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)     # fgo_allreduce_fn
 
 
@@ -313,6 +328,12 @@ def _load():
                                        C.c_int64, C.POINTER(MapResult), dp, u8p, C.POINTER(C.c_int32), i64p, i64p, dp]
     lib.fgo_debug_map_fuse_kernel_ms.restype = C.c_double
     lib.fgo_debug_map_fuse_kernel_ms.argtypes = []
+    lib.fgo_map_clean_params_default.restype = None
+    lib.fgo_map_clean_params_default.argtypes = [C.POINTER(MapCleanParams)]
+    lib.fgo_map_clean.argtypes = [C.c_int, C.c_int64, dp, C.POINTER(MapCleanParams), C.POINTER(MapCleanResult), C.POINTER(C.c_int32), u8p,
+                                  C.POINTER(C.c_int32), i64p, dp]
+    lib.fgo_debug_map_clean_kernel_ms.restype = C.c_double
+    lib.fgo_debug_map_clean_kernel_ms.argtypes = []
     lib.fgo_add_vec3.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_bias.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_prior_vec3.argtypes = [C.c_void_p, C.c_int64, dp, C.c_double]
@@ -918,6 +939,51 @@ def map_fuse_batch(depth, pose_w, color=None, extrinsic=None, params=None, max_v
         out["key"] = key[:m]
     if rt is not None:
         out["rt"] = rt
+    return out
+
+
+def map_clean_params(**kw):
+    """fgo_map_clean_params_default, with the given fields replaced"""
+    p = MapCleanParams()
+    lib.fgo_map_clean_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(MapCleanParams._fields_):
+            raise TypeError("fgo_map_clean_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def map_clean(xyz, color=None, count=None, params=None, device=0):
+    """fgo_map_clean: cluster filtering and floor removal of a cloud in one call.  xyz is n x 3 (map_fuse_batch's "xyz", or any
+    cloud), color (n or n x channels) and count (n) ride along when given.  Returns a dict: label (n, int32; -1 out of range), reason
+    (n, uint8: 0 kept, 1 out of range, 2 cluster size, 3 floor), cluster_size (n_clusters, int32), index (n_kept, int64, ascending),
+    xyz (n_kept x 3, the floor at zero of the up axis), color and count gathered through index (None when not given); and the
+    result fields n_points, n_out_of_range, n_cells, n_clusters, n_clusters_kept, n_after_clusters, n_floor_removed, n_kept,
+    floor_bin, floor_bin_points, floor_height."""
+    x = np.ascontiguousarray(xyz, np.float64)
+    if x.ndim != 2 or x.shape[1] != 3:
+        raise FgoError("map_clean: xyz is n x 3")
+    n = len(x)
+    col = None if color is None else np.asarray(color)
+    if col is not None and (col.ndim not in (1, 2) or len(col) != n):
+        raise FgoError("map_clean: color needs one row per point")
+    cnt = None if count is None else np.asarray(count)
+    if cnt is not None and cnt.shape != (n,):
+        raise FgoError("map_clean: count needs one entry per point")
+    if params is None:
+        params = map_clean_params()
+    label = np.zeros(n, np.int32); reason = np.zeros(n, np.uint8); csize = np.zeros(n, np.int32)
+    index = np.zeros(n, np.int64); out_xyz = np.zeros((n, 3))
+    res = MapCleanResult()
+    i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    rc = lib.fgo_map_clean(device, n, _dp(x), C.byref(params), C.byref(res), i32(label), reason.ctypes.data_as(C.POINTER(C.c_uint8)),
+                           i32(csize), _i64p(index), _dp(out_xyz))
+    if rc < 0:
+        raise FgoError("fgo_map_clean failed: %d" % rc)
+    out = {f: getattr(res, f) for f, _ in MapCleanResult._fields_}
+    index = index[:res.n_kept]
+    out.update(label=label, reason=reason, cluster_size=csize[:res.n_clusters], index=index, xyz=out_xyz[:res.n_kept],
+               color=None if col is None else col[index], count=None if cnt is None else cnt[index])
     return out
 
 

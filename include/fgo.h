@@ -622,8 +622,9 @@ double fgo_debug_match_kernel_ms(void);
  * DEFINITION, pinned to the numpy restatement tests/map_fuse_reference.py.  Where they differ from the reference: its grid is aligned
  * to the cloud's bounding box and its arithmetic is in float, ours is world-aligned (voxel i covers [i, i + 1) leaves from the
  * world's origin) with integer sums; it re-filters the accumulated map after each frame (an unweighted centroid of centroids), ours
- * is ONE centroid per voxel over all points of all frames; lens distortion, the median filter of mapping_PLY_rs.cpp:172 and the
- * clustering of pcd_filter.cpp are out of scope (min_points stands in for the last); the caller chooses the frames (trajectory_skip).
+ * is ONE centroid per voxel over all points of all frames; lens distortion and the median filter of mapping_PLY_rs.cpp:172
+ * are out of scope; the clustering and floor removal of pcd_filter.cpp are fgo_map_clean below (min_points only drops thin voxels);
+ * the caller chooses the frames (trajectory_skip).
  *   pose        frame f has pose_w7[f] = t_w(3) q_xyzw(4), as fgo_get_poses gives it; extrinsic7 (t_e, q_e) is Pu2c, NULL = identity.
  *               A quaternion is normalised on entry: each component divided by sqrt(((qx qx + qy qy) + qz qz) + qw qw).  With the
  *               normalised (x, y, z, w):  R00 = 1 - 2 (y y + z z)  R01 = 2 (x y - z w)      R02 = 2 (x z + y w)
@@ -685,6 +686,70 @@ int fgo_map_fuse_batch(int device, int64_t n_frames, int width, int height,
                        int64_t *frame_points_out /* n, may be NULL */, double *rt_out /* n x 12, may be NULL */);
 /* development: the device time of the last fgo_map_fuse_batch call by HIP events (table init, insert, pack; sort, finalise), ms */
 double fgo_debug_map_fuse_kernel_ms(void);
+
+/* Cluster filtering and floor removal of the fused map: the program that ends the reference's run, mapping/pcd_filter.cpp:44-66,95-99
+ * (clusterFilter(0.03, ...) = pcl::EuclideanClusterExtraction with setMinClusterSize(200): the points whose cluster has at least 200
+ * members stay, the flying pixels go) and :107-172 (remove_floor_pt: the floor is the most populated bin of a histogram of z at
+ * res = 0.1, everything up to 0.1 above it is dropped and the floor becomes the zero of z), in ONE call on the device.  The call
+ * takes ANY cloud of n_points rows, not only fgo_map_fuse_batch's xyz_out; colour and count are not arguments, the caller gathers
+ * them through index_out.  PCL is not part of the reference tree, so the semantics below are THIS PROJECT'S DEFINITION, pinned to the
+ * numpy restatement tests/map_clean_reference.py.  Everything that decides an outcome is integer arithmetic.  Where they differ
+ * from the reference: it works in float, ours on the 2^-20 m quantum; its clamp of max_z to min_z + 2 (:124) feeds only n_bins, which
+ * is printed and never used, so it bins EVERY point (:130-135) -- ours looks for the floor in the lowest floor_span only, which is
+ * what that clamp was evidently for; its up axis is z, ours is a parameter (the camera's y points down).
+ *   quantum     Q_k = llrint(x_k 2^20), ties to even, as in map fusion.  T = llrint(tolerance 2^20).  The cell of a point is
+ *               c_k = floor(Q_k / T), floor division of the QUANTISED coordinate (Q = -1 is in cell -1), and its key
+ *               ((c_z + 2^20) << 42) | ((c_y + 2^20) << 21) | (c_x + 2^20).  A point is OUT OF RANGE if a coordinate is not finite,
+ *               if |x_k 2^20| >= 2^62 or if some |c_k| >= 2^20: reason 1, label -1, counted in n_out_of_range, and it takes no
+ *               further part.  n_cells counts the occupied cells.
+ *   link        two in-range points are linked iff dQ_x^2 + dQ_y^2 + dQ_z^2 <= T^2 in 64-bit integers: PCL's closed radius.
+ *               Coincident points are linked.  The link is symmetric and exact; linked points lie in the same or in adjacent
+ *               cells (27 cells); tolerance in [2^-20, 256] keeps every intermediate below 2^63.
+ *   clusters    the connected components of the link graph, numbered 0, 1, ... in ascending order of their SMALLEST member's input
+ *               index, the small ones too.  label_out[p] is that number, cluster_size_out[c] the size of cluster c, n_clusters
+ *               their number.  A cluster is kept iff min_cluster_size <= size and (max_cluster_size == 0 or size <=
+ *               max_cluster_size), both bounds included as in PCL; n_clusters_kept counts those.  The points of the others get
+ *               reason 2; n_after_clusters points survive this stage.
+ *   floor       only with remove_floor and n_after_clusters > 0 (else floor_bin = -1, floor_bin_points = 0, floor_height = 0), over
+ *               the points that survived the cluster stage.  h_p = up_sign Q_up_axis(p), h_min their minimum.  R = llrint(floor_res
+ *               2^20), S = llrint(floor_span 2^20), C = llrint(floor_clearance 2^20).  bin(p) = (h_p - h_min + R div 2) div R, and
+ *               a point is counted only if h_p - h_min <= S.  floor_bin is the LOWEST index among the most populated bins (the
+ *               reference's std::map walk with > does the same), floor_bin_points its count.  F = h_min + floor_bin R,
+ *               floor_height = (double)F 2^-20.  A point is kept iff h_p > F + C, strictly; otherwise reason 3, counted in
+ *               n_floor_removed.  The up-axis coordinate of a kept point's row of xyz_out is x - up_sign floor_height, one
+ *               subtraction rounded once; the other two coordinates are copied bit for bit (all three without the floor stage).
+ *   output      kept points have reason 0 and appear in ASCENDING INPUT INDEX: index_out their indices, xyz_out their rows,
+ *               n_kept their number.  n_kept + n_floor_removed = n_after_clusters.
+ * Two calls give bit-identical outputs.  Under a permutation of the input the kept SET, the partition and every count are the
+ * same; labels and index_out map through the permutation.  Stateless, host arrays in and out; only the n_clusters sizes and the
+ * n_kept rows are copied back.  FGO_EINVAL (before any HIP call): result NULL, n_points < 0 or >= 2^30, xyz NULL with n_points > 0,
+ * tolerance outside [2^-20, 256] or not finite, min_cluster_size < 1, max_cluster_size < 0 or in [1, min_cluster_size), up_axis not
+ * 0, 1 or 2, up_sign not +1 or -1, remove_floor not 0 or 1; and with remove_floor: floor_res outside [2^-20, 1024], floor_span < 0,
+ * floor_span / floor_res > 4096, floor_clearance < 0, any of the three not finite.  n_points == 0: FGO_OK and a zero result with
+ * floor_bin = -1.  FGO_ENODEV without a HIP device (no CPU fallback).  FGO_ENOMEM: the call needs about 170 bytes of device memory
+ * per point. */
+typedef struct {
+  double tolerance;        /* 0.03 m   clusterFilter(0.03, ...)                       */
+  int min_cluster_size;    /* 200      setMinClusterSize; 1 keeps every cluster        */
+  int max_cluster_size;    /* 0 = no upper bound (PCL's default)                       */
+  int remove_floor;        /* 1                                                        */
+  int up_axis, up_sign;    /* 2, +1    height h = up_sign * coordinate[up_axis]        */
+  double floor_res;        /* 0.1 m    res                                             */
+  double floor_span;       /* 2.0 m    the floor is looked for in the lowest span      */
+  double floor_clearance;  /* 0.1 m    keep h > floor + clearance                      */
+} fgo_map_clean_params;
+void fgo_map_clean_params_default(fgo_map_clean_params *p);   /* NULL tolerated */
+typedef struct {
+  int64_t n_points, n_out_of_range, n_cells, n_clusters, n_clusters_kept, n_after_clusters, n_floor_removed, n_kept;
+  int64_t floor_bin /* -1: no floor stage */, floor_bin_points;
+  double floor_height;
+} fgo_map_clean_result;
+int fgo_map_clean(int device, int64_t n_points, const double *xyz /* n x 3 */, const fgo_map_clean_params *params /* NULL = defaults */,
+                  fgo_map_clean_result *result /* 1 */, int32_t *label_out /* n, may be NULL */, uint8_t *reason_out /* n, may be NULL */,
+                  int32_t *cluster_size_out /* n (n_clusters written), may be NULL */,
+                  int64_t *index_out /* n (n_kept written), may be NULL */, double *xyz_out /* n x 3 (n_kept rows), may be NULL */);
+/* development: the device time of the last fgo_map_clean call by HIP events (quantise to compact), ms */
+double fgo_debug_map_clean_kernel_ms(void);
 
 /* LevenbergMarquardtOptimizer(graph, values).optimize() with GTSAM 4.0's default parameters —
  *      CGraphGT::optimizeGraphBatch, gtsam/gtsam_graph.cpp:1784-1788.  max_iters <= 0 selects the default 100.
