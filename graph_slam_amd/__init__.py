@@ -195,6 +195,17 @@ class MapCleanResult(C.Structure):
                 ("floor_bin", C.c_int64), ("floor_bin_points", C.c_int64), ("floor_height", C.c_double)]
 
 
+class MapNormalsParams(C.Structure):
+    """fgo_map_normals_params"""
+    _fields_ = [("k", C.c_int), ("max_radius", C.c_double), ("cell", C.c_double), ("viewpoint", C.c_double * 3)]
+
+
+class MapNormalsResult(C.Structure):
+    """fgo_map_normals_result"""
+    _fields_ = [("n_points", C.c_int64), ("n_out_of_range", C.c_int64), ("n_cells", C.c_int64), ("n_valid", C.c_int64),
+                ("n_few", C.c_int64), ("n_degenerate", C.c_int64)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)     # fgo_allreduce_fn
 
 
@@ -334,6 +345,12 @@ def _load():
                                   C.POINTER(C.c_int32), i64p, dp]
     lib.fgo_debug_map_clean_kernel_ms.restype = C.c_double
     lib.fgo_debug_map_clean_kernel_ms.argtypes = []
+    lib.fgo_map_normals_params_default.restype = None
+    lib.fgo_map_normals_params_default.argtypes = [C.POINTER(MapNormalsParams)]
+    lib.fgo_map_normals.argtypes = [C.c_int, C.c_int64, dp, C.POINTER(MapNormalsParams), C.POINTER(MapNormalsResult), dp, dp, dp, i32p, u8p,
+                                    i32p, i64p, i64p]
+    lib.fgo_debug_map_normals_kernel_ms.restype = C.c_double
+    lib.fgo_debug_map_normals_kernel_ms.argtypes = []
     lib.fgo_add_vec3.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_bias.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_prior_vec3.argtypes = [C.c_void_p, C.c_int64, dp, C.c_double]
@@ -987,9 +1004,56 @@ def map_clean(xyz, color=None, count=None, params=None, device=0):
     return out
 
 
-def write_ply(path, xyz, color=None):
+def map_normals_params(**kw):
+    """fgo_map_normals_params_default, with the given fields replaced (viewpoint: 3 numbers)"""
+    p = MapNormalsParams()
+    lib.fgo_map_normals_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(MapNormalsParams._fields_):
+            raise TypeError("fgo_map_normals_params has no field %r" % k)
+        setattr(p, k, (C.c_double * 3)(*v) if k == "viewpoint" else v)
+    return p
+
+
+def map_normals(xyz, params=None, want_neighbours=False, want_scatter=False, device=0):
+    """fgo_map_normals: the k nearest neighbours of every point of a cloud and the surface normal and curvature fitted to them, in
+    one call.  xyz is n x 3 (map_clean's "xyz", or any cloud).  Returns a dict: normal (n x 3, unit, turned towards the viewpoint),
+    curvature (n), eigenvalues (n x 3, ascending), n_neighbours (n, int32), status (n, uint8: 0 valid, 1 out of range, 2 fewer than 3
+    neighbours, 3 all neighbours coincide; NaN in the floating outputs unless 0); with want_neighbours neighbour (n x k, int32, the
+    point itself included, padded with -1) and dist2 (n x k, int64, squared distances in quanta of 2^-20 m), with want_scatter
+    scatter (n x 6, int64); and the result fields n_points, n_out_of_range, n_cells, n_valid, n_few, n_degenerate."""
+    x = np.ascontiguousarray(xyz, np.float64)
+    if x.ndim != 2 or x.shape[1] != 3:
+        raise FgoError("map_normals: xyz is n x 3")
+    n = len(x)
+    if params is None:
+        params = map_normals_params()
+    k = max(int(params.k), 0)
+    normal = np.zeros((n, 3)); curv = np.zeros(n); eig = np.zeros((n, 3))
+    nn = np.zeros(n, np.int32); status = np.zeros(n, np.uint8)
+    nb = np.zeros((n, k), np.int32) if want_neighbours else None
+    d2 = np.zeros((n, k), np.int64) if want_neighbours else None
+    sc = np.zeros((n, 6), np.int64) if want_scatter else None
+    res = MapNormalsResult()
+    rc = lib.fgo_map_normals(device, n, _dp(x), C.byref(params), C.byref(res), _dp(normal), _dp(curv), _dp(eig),
+                             nn.ctypes.data_as(C.POINTER(C.c_int32)), status.ctypes.data_as(C.POINTER(C.c_uint8)),
+                             None if nb is None else nb.ctypes.data_as(C.POINTER(C.c_int32)), None if d2 is None else _i64p(d2),
+                             None if sc is None else _i64p(sc))
+    if rc < 0:
+        raise FgoError("fgo_map_normals failed: %d" % rc)
+    out = {f: getattr(res, f) for f, _ in MapNormalsResult._fields_}
+    out.update(normal=normal, curvature=curv, eigenvalues=eig, n_neighbours=nn, status=status)
+    if want_neighbours:
+        out.update(neighbour=nb, dist2=d2)
+    if want_scatter:
+        out["scatter"] = sc
+    return out
+
+
+def write_ply(path, xyz, color=None, normals=None):
     """an ASCII PLY in the layout of the reference's headerPLY (mapping/mapping_PCD.cpp:169-181): float x y z, uchar red green blue.
-    color is m x 3, m or m x 1 (grey, repeated three times) or None (255)."""
+    color is m x 3, m or m x 1 (grey, repeated three times) or None (255).  With normals (m x 3: map_normals' "normal") the vertex
+    also has float nx ny nz after z, the XYZ+RGB+normal cloud of pcd2mesh.cpp:65-67; without, the file is what it always was."""
     xyz = np.asarray(xyz, np.float64).reshape(-1, 3)
     m = len(xyz)
     if color is None:
@@ -1000,11 +1064,22 @@ def write_ply(path, xyz, color=None):
             rgb = np.repeat(rgb, 3, 1)
         if rgb.shape[1] != 3:
             raise FgoError("write_ply: color is m x 3 or m")
+    nrm = None
+    if normals is not None:
+        nrm = np.asarray(normals, np.float64)
+        if nrm.shape != (m, 3):
+            raise FgoError("write_ply: normals is m x 3")
     with open(path, "w") as f:
-        f.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-                "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % m)
-        for p, c in zip(xyz, rgb):
-            f.write("%.9g %.9g %.9g %d %d %d\n" % (p[0], p[1], p[2], c[0], c[1], c[2]))
+        f.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % m)
+        if nrm is not None:
+            f.write("property float nx\nproperty float ny\nproperty float nz\n")
+        f.write("property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+        if nrm is None:
+            for p, c in zip(xyz, rgb):
+                f.write("%.9g %.9g %.9g %d %d %d\n" % (p[0], p[1], p[2], c[0], c[1], c[2]))
+        else:
+            for p, v, c in zip(xyz, nrm, rgb):
+                f.write("%.9g %.9g %.9g %.9g %.9g %.9g %d %d %d\n" % (p[0], p[1], p[2], v[0], v[1], v[2], c[0], c[1], c[2]))
 
 
 def synth_manhattan3d(n_poses, lookback=5, n_loop=4, seed=42, sigma_t=0.02, sigma_q=0.005):

@@ -8,8 +8,8 @@
 //   sort      rocPRIM's radix sort of the (cell key, input index) pairs.  It is stable, so a cell's run is in ascending input index;
 //             the out-of-range mark is the largest key and sorts behind every cell.
 //   cells     the quantised coordinates are gathered into sorted order and the run heads are counted.  A cell's run is found by
-//             binary search of the sorted keys: neighbouring lanes look for neighbouring cells, so the upper levels of the search
-//             stay in cache.  An open-addressing table cell key -> start of the run (64-bit atomicCAS on the key, two slots per
+//             binary search of the sorted keys (map_cells_device.hpp, shared with kernels_map_normals.hip, as are the floor
+//             division and the key): neighbouring lanes look for neighbouring cells, so the upper levels of the search stay in cache.  An open-addressing table cell key -> start of the run (64-bit atomicCAS on the key, two slots per
 //             point) was built and measured as well: 5 % faster on a map of 44 000 points, 11 % slower on a sheet of 2 000 000,
 //             24 to 48 more bytes per point; it is not kept (the figures of both: profiles/NOTES.md).
 //   link      one lane per point in sorted order: it walks back over the points of its own cell that precede it and over the 13
@@ -38,13 +38,16 @@
 #include <cstring>
 #include "../../include/fgo.h"
 #include "batch_call.hpp"
+#include "map_cells_device.hpp"
 
 namespace fgo {
 namespace {
 
+using dev::map_cell_key;
+
 constexpr int MC_T = 256;                        // threads of a workgroup
-constexpr long long MC_IMAX = 1ll << 20;         // |c_k| < 2^20
-constexpr unsigned long long MC_EMPTY = ~0ull;   // the key of an out-of-range point: behind every cell in sorted order
+constexpr long long MC_IMAX = dev::MAP_CELL_BIAS; // |c_k| < 2^20
+constexpr unsigned long long MC_EMPTY = dev::MAP_CELL_EMPTY;      // the key of an out-of-range point: behind every cell in sorted order
 constexpr uint32_t MC_NONE = ~0u;                // no such cell
 constexpr unsigned MC_MAX_GRID = 1u << 20;       // workgroups of a launch; the kernels stride beyond that
 constexpr int MC_MAX_BINS = 8192;                // floor_span / floor_res <= 4096 gives at most 6145 bins (R = 1, S = 6144)
@@ -91,15 +94,13 @@ __global__ __launch_bounds__(MC_T) void k_mc_quantise(McArgs A) {
       long long Q = 0;
       if (fabs(y) < 4611686018427387904.0) {                       // finite and below 2^62
         Q = llrint(y);                                             // ties to even
-        long long q = Q / A.T;
-        if (Q - q * A.T < 0) --q;                                  // floor division
+        const long long q = dev::map_floor_div(Q, A.T);
         if (q <= -MC_IMAX || q >= MC_IMAX) ok = false;
         c[k] = q;
       } else ok = false;
       A.Q[3 * p + k] = Q;
     }
-    A.key[p] = ok ? ((unsigned long long)(c[2] + MC_IMAX) << 42) | ((unsigned long long)(c[1] + MC_IMAX) << 21) | (unsigned long long)(c[0] + MC_IMAX)
-                  : MC_EMPTY;
+    A.key[p] = ok ? map_cell_key(c[0] + MC_IMAX, c[1] + MC_IMAX, c[2] + MC_IMAX) : MC_EMPTY;
     A.idx[p] = (uint32_t)p;
     A.parent[p] = (int32_t)p;
     A.size[p] = 0;
@@ -122,11 +123,7 @@ __global__ __launch_bounds__(MC_T) void k_mc_cells(McArgs A) {
 
 // the start of the run of `key` in sorted order, or MC_NONE
 __device__ inline uint32_t mc_lookup(const McArgs &A, unsigned long long key) {
-  int64_t lo = 0, hi = A.n;                                                             // the first s with skey[s] >= key
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (A.skey[mid] < key) lo = mid + 1; else hi = mid;
-  }
+  const int64_t lo = dev::map_key_lower_bound(A.skey, A.n, key);                        // the first s with skey[s] >= key
   return lo < A.n && A.skey[lo] == key ? (uint32_t)lo : MC_NONE;
 }
 
@@ -172,7 +169,7 @@ __global__ __launch_bounds__(MC_T) void k_mc_link(McArgs A) {
     for (int t = 0; t < 13; ++t) {                                             // the neighbour cells before its own in key order
       const long long e[3] = {c[0] + t % 3 - 1, c[1] + (t / 3) % 3 - 1, c[2] + t / 9 - 1};
       if (e[0] < 1 || e[1] < 1 || e[2] < 1 || e[0] >= 2 * MC_IMAX || e[1] >= 2 * MC_IMAX || e[2] >= 2 * MC_IMAX) continue;   // no such cell
-      const unsigned long long nkey = ((unsigned long long)e[2] << 42) | ((unsigned long long)e[1] << 21) | (unsigned long long)e[0];
+      const unsigned long long nkey = map_cell_key(e[0], e[1], e[2]);
       const uint32_t j0 = mc_lookup(A, nkey);
       if (j0 == MC_NONE) continue;
       for (int64_t j = j0; j < A.n && A.skey[j] == nkey; ++j) visit(j);

@@ -751,6 +751,61 @@ int fgo_map_clean(int device, int64_t n_points, const double *xyz /* n x 3 */, c
 /* development: the device time of the last fgo_map_clean call by HIP events (quantise to compact), ms */
 double fgo_debug_map_clean_kernel_ms(void);
 
+/* k-nearest-neighbour surface normals of the map: the first half of mapping/pcd2mesh.cpp:52-67 (pcl::NormalEstimation with a kd-tree
+ * and setKSearch(20): a surface normal and a curvature for every point; concatenateFields is the caller's, see write_ply in the
+ * Python package), in ONE call on the device.  The greedy triangulation of the second half is a sequential front-growing algorithm
+ * and out of scope.  The call takes ANY cloud of n_points rows; with neighbour_out it is a k-nearest-neighbour query of the cloud
+ * on its own.  PCL is not part of the reference tree, so the semantics below are THIS PROJECT'S DEFINITION, pinned to the numpy
+ * restatement tests/map_normals_reference.py.  Where they differ from PCL: distances are integers on the 2^-20 m quantum and ties
+ * have a stated order; the neighbours lie within max_radius (PCL's k-search has no bound); the covariance is the exact integer
+ * scatter, converted once.
+ *   quantum     Q_k = llrint(x_k 2^20), ties to even, the product rounded on its own, as in map fusion and cleaning.  A point is
+ *               IN RANGE iff every coordinate is finite and every |Q_k| < 2^34 (16384 m).  Any other point has status 1, is counted
+ *               in n_out_of_range, is nobody's neighbour and has none: n_neighbours 0, its rows of neighbour_out and dist2_out
+ *               all -1, of scatter_out 0.  The range does not depend on cell.  n_cells counts the occupied search cells
+ *               (c_k = floor(Q_k / llrint(cell 2^20))): the only output that depends on cell.
+ *   neighbours  the neighbours of the in-range point p are the first min(k, .) in-range points q, p ITSELF INCLUDED (as in PCL),
+ *               in ascending order of the pair (d2, input index of q), where d2 = dQ_x^2 + dQ_y^2 + dQ_z^2, dQ = Q(q) - Q(p), in
+ *               64-bit integers, among the points with d2 <= Rq^2, Rq = llrint(max_radius 2^20): the radius is closed, ties in d2
+ *               go to the smaller input index.  n_neighbours_out[p] = m is their number; neighbour_out[p] and dist2_out[p] hold
+ *               them in that order, the tail padded with -1.  With max_radius <= 16 and k <= 64 every integer here stays below 2^63.
+ *   scatter     S1 = sum dQ, S2 = sum dQ dQ^T over the m neighbours, M = m S2 - S1 S1^T: exact in int64, whatever the order of
+ *               summation.  scatter_out[p] is its upper triangle xx xy xz yy yz zz (for status 2 and 3 too).
+ *   status      0 valid; 1 out of range; 2 few: m < 3 (whatever M is); 3 degenerate: m >= 3 and M is the zero matrix, that is, all
+ *               neighbours coincide.  For 1, 2 and 3 the normal, the curvature and the eigenvalues are NaN.  n_valid, n_few and
+ *               n_degenerate count status 0, 2 and 3.
+ *   fit         for status 0: A_ij = (double)M_ij / ((double)(m m) 2^40), each entry converted once, then divided once: the
+ *               covariance of the neighbours in m^2.  eigenvalues_out = l0 <= l1 <= l2 of A by 8 sweeps of the cyclic Jacobi
+ *               rotation (pairs 01, 02, 12) every plane fit of this library uses; normal_out = the eigenvector e of l0 divided by
+ *               sqrt((e_x e_x + e_y e_y) + e_z e_z); curvature_out = l0 / ((l0 + l1) + l2).  Sign: d_k = viewpoint_k -
+ *               (double)Q_k 2^-20, s = (n_x d_x + n_y d_y) + n_z d_z; the normal is negated if s < 0, and if s == 0 exactly, if its
+ *               first non-zero component is negative: n.(viewpoint - p) >= 0 always.  Every product, quotient and sum is rounded
+ *               to double on its own: the kernel does not contract them.  Rounding may leave l0 a few ulps of l2 below zero.
+ * Two calls give bit-identical outputs.  Every output but n_cells is bit-identical for every admissible cell: cell only tunes
+ * the search.  Under a permutation of the input every output maps through the permutation exactly, provided that no point has a
+ * tie in d2 at the place where its list ends.  Stateless, host arrays in and out.  FGO_EINVAL (before any HIP call): result NULL,
+ * n_points < 0 or >= 2^30, xyz NULL with n_points > 0, normal_out, curvature_out, n_neighbours_out or status_out NULL with
+ * n_points > 0, k outside [3, 64], max_radius outside [2^-20, 16] or not finite, cell outside [2^-6, 16] or not finite (so that
+ * floor(Q / T_cell) fits the 21-bit cell fields), max_radius / cell > 16 (the search visits at most 17 rings of cells), a
+ * viewpoint coordinate not finite.  n_points == 0: FGO_OK and a zero result.  FGO_ENODEV without a HIP device (no CPU fallback).
+ * FGO_ENOMEM: the call needs about 200 bytes of device memory per point, and 12 k + 48 more with all optional outputs. */
+typedef struct {
+  int k;                 /* 20     setKSearch(20), pcd2mesh.cpp:59; the point itself is one of the k, as in PCL */
+  double max_radius;     /* 0.16 m neighbours lie within this closed radius; PCL has no such bound (stated difference) */
+  double cell;           /* 0.04 m side of the search cells: tuning only, NO output but n_cells depends on it */
+  double viewpoint[3];   /* 0,0,0  PCL's default viewpoint: normals are turned towards it */
+} fgo_map_normals_params;
+void fgo_map_normals_params_default(fgo_map_normals_params *p);   /* NULL tolerated */
+typedef struct { int64_t n_points, n_out_of_range, n_cells, n_valid, n_few, n_degenerate; } fgo_map_normals_result;
+int fgo_map_normals(int device, int64_t n_points, const double *xyz /* n x 3 */, const fgo_map_normals_params *params /* NULL = defaults */,
+                    fgo_map_normals_result *result /* 1 */,
+                    double *normal_out /* n x 3 */, double *curvature_out /* n */, double *eigenvalues_out /* n x 3, may be NULL */,
+                    int32_t *n_neighbours_out /* n */, uint8_t *status_out /* n */,
+                    int32_t *neighbour_out /* n x k, may be NULL */, int64_t *dist2_out /* n x k, may be NULL */,
+                    int64_t *scatter_out /* n x 6, may be NULL */);
+/* development: the device time of the last fgo_map_normals call by HIP events (quantise to fit), ms */
+double fgo_debug_map_normals_kernel_ms(void);
+
 /* LevenbergMarquardtOptimizer(graph, values).optimize() with GTSAM 4.0's default parameters —
  *      CGraphGT::optimizeGraphBatch, gtsam/gtsam_graph.cpp:1784-1788.  max_iters <= 0 selects the default 100.
  *      Returns the number of iterations performed or a negative code. */
