@@ -206,6 +206,26 @@ class MapNormalsResult(C.Structure):
                 ("n_few", C.c_int64), ("n_degenerate", C.c_int64)]
 
 
+class MapRenderParams(C.Structure):
+    """fgo_map_render_params"""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("z_scale", C.c_double),
+                ("z_min", C.c_double), ("z_max", C.c_double), ("splat", C.c_int), ("radius", C.c_double), ("max_half", C.c_int),
+                ("agree_tol", C.c_double), ("background", C.c_uint8 * 3)]
+
+
+class MapRenderView(C.Structure):
+    """fgo_map_render_view"""
+    _fields_ = [(f, C.c_int64) for f in ("n_valid", "n_drawn", "n_pixels", "n_meas", "n_both", "n_agree", "n_closer", "n_through")]
+
+
+class MapRenderResult(C.Structure):
+    """fgo_map_render_result"""
+    _fields_ = [("n_points", C.c_int64), ("n_nonfinite", C.c_int64), ("form", C.c_int), ("tile_rows", C.c_int)]
+
+
+FGO_MAP_RENDER_TILES, FGO_MAP_RENDER_GLOBAL = 0, 1
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)     # fgo_allreduce_fn
 
 
@@ -351,6 +371,13 @@ def _load():
                                     i32p, i64p, i64p]
     lib.fgo_debug_map_normals_kernel_ms.restype = C.c_double
     lib.fgo_debug_map_normals_kernel_ms.argtypes = []
+    lib.fgo_map_render_params_default.restype = None
+    lib.fgo_map_render_params_default.argtypes = [C.POINTER(MapRenderParams)]
+    lib.fgo_map_render_batch.argtypes = [C.c_int, C.c_int64, dp, u8p, C.c_int, C.c_int64, dp, dp, dp, C.c_int, C.c_int,
+                                         C.POINTER(MapRenderParams), C.POINTER(C.c_uint16), C.POINTER(MapRenderResult),
+                                         C.POINTER(MapRenderView), i32p, i32p, u8p, dp]
+    lib.fgo_debug_map_render_kernel_ms.restype = C.c_double
+    lib.fgo_debug_map_render_kernel_ms.argtypes = []
     lib.fgo_add_vec3.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_bias.argtypes = [C.c_void_p, C.c_int64, dp]
     lib.fgo_add_prior_vec3.argtypes = [C.c_void_p, C.c_int64, dp, C.c_double]
@@ -1048,6 +1075,135 @@ def map_normals(xyz, params=None, want_neighbours=False, want_scatter=False, dev
     if want_scatter:
         out["scatter"] = sc
     return out
+
+
+def map_render_params(**kw):
+    """fgo_map_render_params_default, with the given fields replaced (background: 3 numbers)"""
+    p = MapRenderParams()
+    lib.fgo_map_render_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(MapRenderParams._fields_):
+            raise TypeError("fgo_map_render_params has no field %r" % k)
+        setattr(p, k, (C.c_uint8 * 3)(*v) if k == "background" else v)
+    return p
+
+
+def map_render_batch(xyz, pose_w, color=None, extrinsic=None, view_offset=None, width=176, height=144, params=None, depth=None,
+                     want_zq=True, want_index=False, want_color=None, want_rt=False, device=0):
+    """fgo_map_render_batch: the cloud drawn from every pose in one call, by a z-buffer.  xyz is n x 3 (map_fuse_batch's "xyz", or any
+    cloud), color None, n (grey) or n x 3 (uint8), pose_w V x 7 (t, q_xyzw: Graph.get_poses, or a list of look_at poses), extrinsic
+    the 7 numbers of Pu2c or None, view_offset a further pose composed on the right or None (look_at((0, -2, -5), (0, 0, 5),
+    (0, -0.98, 0.199)) is the reference's chase camera), depth None or V x H x W uint16 measured depth words to check the map
+    against.  want_color defaults to whether color is given.  Returns a dict: with want_zq zq (V x H x W, int32: the depth in quanta
+    of 2^-20 m, -1 where nothing was drawn), with want_index index (V x H x W, int32, the drawn point or -1), with want_color color
+    (V x H x W x channels, uint8; V x H x W for grey), with want_rt rt (V x 12); the per-view counts n_valid, n_drawn, n_pixels,
+    n_meas, n_both, n_agree, n_closer, n_through (V, int64); and the result fields n_points, n_nonfinite, form, tile_rows."""
+    x = np.ascontiguousarray(xyz, np.float64)
+    if x.ndim != 2 or x.shape[1] != 3:
+        raise FgoError("map_render_batch: xyz is n x 3")
+    n = len(x)
+    ps = np.ascontiguousarray(pose_w, np.float64)
+    if ps.ndim == 1 and ps.size == 7:
+        ps = ps[None]
+    if ps.ndim != 2 or ps.shape[1] != 7:
+        raise FgoError("map_render_batch: pose_w is V x 7")
+    nv, w, h = len(ps), int(width), int(height)
+    col, ch, grey = None, 0, False
+    if color is not None:
+        col = np.ascontiguousarray(color, np.uint8)
+        grey = col.ndim == 1
+        if col.shape not in ((n,), (n, 1), (n, 3)):
+            raise FgoError("map_render_batch: color is n or n x 3")
+        ch = 3 if col.ndim == 2 and col.shape[1] == 3 else 1
+    if want_color is None:
+        want_color = ch > 0
+    if want_color and ch == 0:
+        raise FgoError("map_render_batch: want_color needs color")
+    ext = None if extrinsic is None else np.ascontiguousarray(extrinsic, np.float64).reshape(7)
+    off = None if view_offset is None else np.ascontiguousarray(view_offset, np.float64).reshape(7)
+    dm = None
+    if depth is not None:
+        dm = np.ascontiguousarray(depth, np.uint16)
+        if dm.shape == (h, w):
+            dm = dm[None]
+        if dm.shape != (nv, h, w):
+            raise FgoError("map_render_batch: depth is V x H x W")
+    if params is None:
+        params = map_render_params()
+    hh, ww = max(h, 0), max(w, 0)                                  # a bad size is the library's to refuse
+    zq = np.zeros((nv, hh, ww), np.int32) if want_zq else None
+    index = np.zeros((nv, hh, ww), np.int32) if want_index else None
+    cout = np.zeros((nv, hh, ww, ch), np.uint8) if want_color else None
+    rt = np.zeros((nv, 12)) if want_rt else None
+    views = (MapRenderView * max(nv, 1))()
+    res = MapRenderResult()
+    u8 = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8))
+    i32 = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    opt = lambda a: None if a is None else _dp(a)
+    rc = lib.fgo_map_render_batch(device, n, _dp(x), u8(col), ch, nv, _dp(ps), opt(ext), opt(off), w, h, C.byref(params),
+                                  None if dm is None else dm.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(res), views, i32(zq),
+                                  i32(index), u8(cout), opt(rt))
+    if rc < 0:
+        raise FgoError("fgo_map_render_batch failed: %d" % rc)
+    out = {f: int(getattr(res, f)) for f, _ in MapRenderResult._fields_}
+    counts = np.frombuffer(views, np.int64).reshape(-1, 8)[:nv]
+    out.update({f: counts[:, k].copy() for k, (f, _) in enumerate(MapRenderView._fields_)})
+    if zq is not None:
+        out["zq"] = zq
+    if index is not None:
+        out["index"] = index
+    if cout is not None:
+        out["color"] = cout[..., 0] if grey else cout
+    if rt is not None:
+        out["rt"] = rt
+    return out
+
+
+def look_at_matrix(eye, target, up):
+    """R = [x y z] (columns) of look_at: z = normalise(target - eye), x = normalise((-up) x z), y = z x x.  x is made orthogonal to
+    z once more after the cross product, so that R stays orthonormal to rounding when up is close to the line of sight."""
+    eye, target, up = (np.asarray(v, np.float64).reshape(3) for v in (eye, target, up))
+    z = target - eye
+    nz = np.linalg.norm(z)
+    x = np.cross(-up, z)
+    nx = np.linalg.norm(x)
+    if not (nz > 0 and nx > 0 and np.isfinite(nz) and np.isfinite(nx)):
+        raise FgoError("look_at: target equals eye, or up is parallel to the line of sight")
+    z = z / nz; x = x / nx
+    x = x - (x @ z) * z
+    x = x / np.linalg.norm(x)
+    return np.stack([x, np.cross(z, x), z], 1)
+
+
+def look_at(eye, target, up):
+    """the pose7 (t, q_xyzw) of a camera at eye that looks at target, in the camera convention of the map calls (x right, y down,
+    z forward): R = look_at_matrix(eye, target, up), t = eye.  As pose_w of map_render_batch it is a camera in the world (a list of
+    them: an arc flown round the map); as view_offset it is a camera placed relative to every pose:
+    look_at((0, -2, -5), (0, 0, 5), (0, -0.98, 0.199)) is the chase camera of the reference's mapping/map_video.cpp:119-127."""
+    R = look_at_matrix(eye, target, up)
+    # the quaternion of R by the branch with the largest denominator
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    if tr > 0:
+        s = 2.0 * np.sqrt(1.0 + tr)
+        q = [(R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s, 0.25 * s]
+    else:
+        i = int(np.argmax(np.diag(R))); j = (i + 1) % 3; k = (i + 2) % 3
+        s = 2.0 * np.sqrt(1.0 + R[i, i] - R[j, j] - R[k, k])
+        q = [0.0, 0.0, 0.0, (R[k, j] - R[j, k]) / s]
+        q[i] = 0.25 * s; q[j] = (R[j, i] + R[i, j]) / s; q[k] = (R[k, i] + R[i, k]) / s
+    q = np.asarray(q)
+    return np.concatenate([np.asarray(eye, np.float64).reshape(3), q / np.linalg.norm(q)])
+
+
+def write_ppm(path, image):
+    """a binary PPM (P6) for an H x W x 3 uint8 image, a binary PGM (P5) for H x W: one frame of map_render_batch's "color", to be
+    looked at without an image library"""
+    im = np.asarray(image)
+    if im.dtype != np.uint8 or not (im.ndim == 2 or (im.ndim == 3 and im.shape[2] == 3)):
+        raise FgoError("write_ppm: image is H x W x 3 or H x W, uint8")
+    with open(path, "wb") as f:
+        f.write(b"%s\n%d %d\n255\n" % (b"P6" if im.ndim == 3 else b"P5", im.shape[1], im.shape[0]))
+        f.write(np.ascontiguousarray(im).tobytes())
 
 
 def write_ply(path, xyz, color=None, normals=None):

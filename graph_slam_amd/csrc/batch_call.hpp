@@ -1,5 +1,5 @@
 // Host-side plumbing shared by the stand-alone fgo_*_batch entry points (two-view BA, plane check, IMU check, VRO RANSAC, descriptor matching, plane
-// extraction, plane propagation, map fusion, map cleaning, map normals): input validators, device selection, and the one device allocation a call stages its arrays in.  An entry point
+// extraction, plane propagation, map fusion, map cleaning, map normals, map rendering): input validators, device selection, and the one device allocation a call stages its arrays in.  An entry point
 // decides every FGO_EINVAL, and n == 0 -> FGO_OK, with the validators alone, before select_device() makes the first HIP call.
 #pragma once
 #include <hip/hip_runtime.h>

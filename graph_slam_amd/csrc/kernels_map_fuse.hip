@@ -34,6 +34,7 @@
 #include <vector>
 #include "../../include/fgo.h"
 #include "batch_call.hpp"
+#include "pose_host.hpp"
 
 namespace fgo {
 namespace {
@@ -228,34 +229,6 @@ __global__ __launch_bounds__(256) void k_map_finalise(const MfSlot *__restrict__
     for (int k = 0; k < ch; ++k) color[j * ch + k] = (uint8_t)((2 * e.c[k] + e.n) / (2 * e.n));
     count[j] = (int32_t)e.n;
     key_out[j] = (int64_t)e.key;
-  }
-}
-
-// R of a quaternion that quat_ok accepted: normalised, then the nine expressions of the header, every operation rounded on its own
-void quat_matrix(const double *q, double R[9]) {
-#pragma clang fp contract(off)
-  const double n = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-  const double x = q[0] / n, y = q[1] / n, z = q[2] / n, w = q[3] / n;
-  R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - z * w); R[2] = 2.0 * (x * z + y * w);
-  R[3] = 2.0 * (x * y + z * w); R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - x * w);
-  R[6] = 2.0 * (x * z - y * w); R[7] = 2.0 * (y * z + x * w); R[8] = 1.0 - 2.0 * (x * x + y * y);
-}
-
-// rt = R row-major, then t, of the pose (times the extrinsic)
-void pose_rt(const double *pose7, const double *ext7, double rt[12]) {
-#pragma clang fp contract(off)
-  double Rw[9];
-  quat_matrix(pose7 + 3, Rw);
-  if (!ext7) {
-    std::memcpy(rt, Rw, sizeof Rw);
-    for (int k = 0; k < 3; ++k) rt[9 + k] = pose7[k];
-    return;
-  }
-  double Re[9];
-  quat_matrix(ext7 + 3, Re);
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) rt[3 * i + j] = (Rw[3 * i] * Re[j] + Rw[3 * i + 1] * Re[3 + j]) + Rw[3 * i + 2] * Re[6 + j];
-    rt[9 + i] = ((Rw[3 * i] * ext7[0] + Rw[3 * i + 1] * ext7[1]) + Rw[3 * i + 2] * ext7[2]) + pose7[i];
   }
 }
 

@@ -806,6 +806,78 @@ int fgo_map_normals(int device, int64_t n_points, const double *xyz /* n x 3 */,
 /* development: the device time of the last fgo_map_normals call by HIP events (quantise to fit), ms */
 double fgo_debug_map_normals_kernel_ms(void);
 
+/* Z-buffer rendering of the map from trajectory poses, batched: what mapping/map_video.cpp, map_video_rs.cpp and map_video_sr.cpp do
+ * with a VTK viewer -- for every pose of the trajectory a camera is placed relative to the sensor (eye (0, -2, -5), looking at
+ * (0, 0, 5), up (0, -0.98, 0.199) in the camera frame, map_video.cpp:119-127,187), the accumulated map is drawn from there, and an
+ * arc is flown round it at the end (:210-238) -- for ALL n_views in ONE call; and the map's self-check: the map drawn from a key
+ * frame's own camera, with that frame's intrinsics, predicts the frame's depth image, and depth_meas is compared with it pixel by
+ * pixel.  The call takes ANY cloud of n_points rows.  PCL and VTK are not part of the reference tree, so the semantics below are
+ * THIS PROJECT'S DEFINITION, pinned to the numpy restatement tests/map_render_reference.py: a point is a square of pixels, a pixel
+ * keeps the nearest point, everything after the projection is integer.  Lines, axes, the window, lens distortion, anti-aliasing,
+ * shading and video encoding are out of scope.
+ *   view        (R1, t1) = the rt of fgo_map_fuse_batch for pose_w7[v] and extrinsic7 (NULL = identity), bit for bit.  view_offset7
+ *               (t_o, q_o; NULL = identity: then (R, t) = (R1, t1)) is a further pose composed on the right -- it carries the chase
+ *               camera: with Ro the matrix of the normalised q_o as in the fusion, R_ij = (R1_i0 Ro_0j + R1_i1 Ro_1j) + R1_i2 Ro_2j
+ *               and t_i = ((R1_i0 to_0 + R1_i1 to_1) + R1_i2 to_2) + t1_i.  This runs on the host, every operation rounded on its own,
+ *               without fused multiply-adds; rt_out[v] = R row-major, then t: exactly what the kernel used.  The camera frame is x
+ *               right, y down, z forward.
+ *   point       a point with a non-finite coordinate is skipped and counted ONCE (not per view) in n_nonfinite.  d_k = x_k - t_k;
+ *               p_k = (R_0k d_0 + R_1k d_1) + R_2k d_2 (R^T d); z = p_2; the point is VALID in the view iff z_min < z < z_max (the
+ *               open interval of the project).  zq = llrint(z 2^20), ties to even.  uf = ((fx p_0) / z) + cx, vf = ((fy p_1) / z) + cy;
+ *               the point is OFF-IMAGE (valid, not drawn) unless -2^30 < uf < 2^30 and -2^30 < vf < 2^30, compared in double (a NaN is
+ *               off-image).  The centre is (u0, v0) = (floor(uf + 0.5), floor(vf + 0.5)).  The half-width is h = min(max_half,
+ *               splat + s), with s = 0 unless radius > 0, then s = floor((fx radius) / z) (taken as max_half where it is larger, an
+ *               infinite quotient included): a sphere of that radius at that depth.  The footprint is the square
+ *               [u0 - h, u0 + h] x [v0 - h, v0 + h] clipped to the image.  EVERY product, quotient and sum is rounded to double
+ *               on its own: the kernels do not contract them.
+ *   pixel       its word is the MINIMUM over all points whose footprint covers it of ((uint64)zq << 32) | (uint32)index: the nearest
+ *               point wins, ties on zq go to the smaller input index; an uncovered pixel is all ones.  zq_out = zq or -1, index_out =
+ *               index or -1, color_out = the winner's colour or background[0 .. channels).
+ *   depth check with depth_meas (NULL: the five counts are zero): zm = w z_scale for the measured word w, valid iff z_min < zm <
+ *               z_max; mq = llrint(zm 2^20), tq = llrint(agree_tol 2^20).  Where a pixel is both measured and covered: it AGREES iff
+ *               |mq - zq| <= tq; the measurement is CLOSER iff mq < zq - tq (something stands in front of the map); it goes THROUGH
+ *               iff mq > zq + tq (the measurement sees through the map: a free-space violation, the signature of a wrong pose).
+ *   counts      per view, int64: n_valid = valid points, n_drawn = valid points whose clipped footprint is not empty, n_pixels =
+ *               covered pixels, n_meas = valid measured pixels, n_both = measured and covered, n_agree + n_closer + n_through = n_both.
+ * result: n_points, n_nonfinite, form = FGO_MAP_RENDER_TILES or _GLOBAL, the kernel form that ran (no output depends on it), and
+ * tile_rows = max(1, 8192 / width), the rows of a strip of the tiles form (0 in the global form).  An image wider than 8192 pixels
+ * runs in the global form.  Two calls give bit-identical outputs; zq_out, color_out (where the pixel's minimum is unique) and every
+ * count are invariant under a permutation of the points.  Each output array may be NULL: it is then neither allocated on the device
+ * nor copied back.  Stateless, host arrays in and out, like fgo_map_fuse_batch.  FGO_EINVAL (before any HIP call): result NULL,
+ * n_points or n_views < 0, n_points >= 2^31, width or height < 1 or their product > 2^24, n_views x width x height >= 2^31, channels
+ * not 0, 1 or 3, fx, fy or z_scale <= 0 or not finite, cx or cy not finite, z_min < 0, z_max > 2047 (so that zq < 2^31), z_min >=
+ * z_max, splat outside [0, 32], max_half outside [splat, 32], radius or agree_tol negative, not finite or > 2047, color_out not NULL
+ * with channels == 0, pose_w7 NULL with n_views > 0, and with n_points > 0 xyz NULL, color NULL with channels > 0 or not NULL with
+ * channels == 0; a zero (or non-finite) quaternion in pose_w7, extrinsic7 or view_offset7.  n_views == 0: FGO_OK and a zero result.
+ * n_points == 0: every view is all background, with zero counts.  FGO_ENODEV without a HIP device (no CPU fallback).  FGO_ENOMEM:
+ * the cloud, the requested outputs (4 + 4 + channels bytes per pixel and view) or, in the global form, the z-buffer do not fit. */
+typedef struct {
+  double fx, fy, cx, cy;   /* 250.5773, 250.5773, 90, 70: the SR4000 pinhole of fgo_map_params */
+  double z_scale;          /* 0.001: metres per word of depth_meas */
+  double z_min, z_max;     /* 0.1, 50: 0 <= z_min < z_max <= 2047 */
+  int splat;               /* 0: half-width of every footprint in pixels, in [0, 32] */
+  double radius;           /* 0.0 m: a point is a sphere of this radius (the map's leaf fills the holes); 0 = off */
+  int max_half;            /* 8: the largest half-width, in [splat, 32] */
+  double agree_tol;        /* 0.05 m */
+  uint8_t background[3];   /* 0, 0, 26 */
+} fgo_map_render_params;
+void fgo_map_render_params_default(fgo_map_render_params *p);   /* NULL tolerated */
+#define FGO_MAP_RENDER_TILES 0   /* a strip of a view per workgroup in an LDS z-buffer */
+#define FGO_MAP_RENDER_GLOBAL 1  /* a device-wide z-buffer, one lane per (view, point) */
+typedef struct { int64_t n_valid, n_drawn, n_pixels, n_meas, n_both, n_agree, n_closer, n_through; } fgo_map_render_view;
+typedef struct { int64_t n_points, n_nonfinite; int form, tile_rows; } fgo_map_render_result;
+int fgo_map_render_batch(int device, int64_t n_points, const double *xyz /* n x 3 */,
+                         const uint8_t *color /* n x channels, NULL iff channels == 0 */, int channels /* 0, 1 or 3 */,
+                         int64_t n_views, const double *pose_w7 /* V x 7: t(3) q_xyzw(4), as fgo_get_poses gives them */,
+                         const double *extrinsic7 /* Pu2c, NULL = identity */, const double *view_offset7 /* NULL = identity */,
+                         int width, int height, const fgo_map_render_params *params /* NULL = defaults */,
+                         const uint16_t *depth_meas /* V x H x W, may be NULL */, fgo_map_render_result *result /* 1 */,
+                         fgo_map_render_view *view_out /* V, may be NULL */, int32_t *zq_out /* V x H x W, may be NULL */,
+                         int32_t *index_out /* V x H x W, may be NULL */, uint8_t *color_out /* V x H x W x channels, may be NULL */,
+                         double *rt_out /* V x 12, may be NULL */);
+/* development: the device time of the last fgo_map_render_batch call by HIP events (all kernels of the call), ms */
+double fgo_debug_map_render_kernel_ms(void);
+
 /* LevenbergMarquardtOptimizer(graph, values).optimize() with GTSAM 4.0's default parameters —
  *      CGraphGT::optimizeGraphBatch, gtsam/gtsam_graph.cpp:1784-1788.  max_iters <= 0 selects the default 100.
  *      Returns the number of iterations performed or a negative code. */
