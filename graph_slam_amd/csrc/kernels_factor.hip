@@ -863,6 +863,9 @@ __global__ __launch_bounds__(NW * 64) void k_panel_tri(DevPlan P, const double *
 //              which every lane picks its MFMA operands:  C(I, K) -= V_I V_K^T, two v_mfma_f64_16x16x4 per live tile.
 // Diagonal tiles are collected in LDS and inverted at the end (16 lanes per tile, right-looking substitution).  Same contract
 // as k_panel_tri (L blocks + ptop), so k_panel_rows, the solves and the backward kernels do not know which one ran.
+// A column is a chain of dependent steps with little to issue beside it, so the kernel is held to TWO waves per SIMD
+// (amdgpu_waves_per_eu(2, 2): 256 registers, no scratch; 19 232 B of LDS, eight workgroups per CU), where one wave's chain
+// fills the other's gaps: tests/test_tri1_resources.py holds the compiler's resource report to that budget.
 constexpr int tri1_tile(int I, int K) { return I * (I + 1) / 2 + K; }
 constexpr int TRI1_NR = 16 * NJMAX;                               // scalar rows incl. the padding of the last tile row
 struct Tri1Ctx {                                                  // wave-uniform / per-lane constants of a panel
@@ -876,6 +879,46 @@ __device__ __forceinline__ const double *tri1_src_row(const Tri1Ctx &X, const in
   const int sc = tsrc[X.rr[h] * PM + k];
   const double *base = sc >= 0 ? X.Lv + 36 * (int64_t)sc : (sc <= -2 ? X.Hblk + 36 * (int64_t)(-2 - sc) : X.Lv + 36 * X.zero_blk);
   return base + 6 * X.rho[h];
+}
+// ---- the 6x6 factor of a column WITHOUT 54 registers of wave-uniform values in every lane (chol6_lds: Lk[21] + invd[6] next to
+// 168 accumulator registers kept the kernel at one wave per SIMD).  Lane i < 6 holds ROW i of the block (the other lanes repeat
+// row 5 and are never read); a pivot and the finished column below it travel to all lanes through v_readlane, i.e. as SCALAR
+// operands of the v_mul / v_fma that use them, and stay in scalar registers for the row TRSM.  Every element sees the
+// operations of chol6_lds on the same values in the same order (d * inv, L_ij * inv, fma(-L_ij, L_kj, L_ik) for ascending j):
+// the same bits.  The chain per pivot grows by two v_readlane pairs.
+__device__ __forceinline__ double tri1_bcast(double v, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+constexpr int tri1_low(int i, int j) { return i * (i - 1) / 2 + j; }   // strictly lower, packed: i > j
+__device__ __forceinline__ bool tri1_chol6(const double *__restrict__ sd, int lane, double (&Ls)[15], double (&invd)[6]) {
+  Row6 row = load_row(&sd[6 * (lane < 5 ? lane : 5)]);
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    const double d = tri1_bcast(row.v[j], j);
+    if (!(d > 0.0)) ok = false;
+    const double inv = rsqrt_nr(d);
+    invd[j] = inv;
+    row.v[j] *= inv;
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+      if (k > j) {
+        const double lkj = tri1_bcast(row.v[j], k);
+        Ls[tri1_low(k, j)] = lkj;
+        row.v[k] = fma(-row.v[j], lkj, row.v[k]);                   // (rows i < k carry values nobody reads)
+      }
+  }
+  return ok;
+}
+__device__ __forceinline__ Row6 tri1_trsm_row(const Row6 &u, const double (&Ls)[15], const double (&invd)[6]) {   // = trsm_row
+  Row6 x, w = u;
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    x.v[c] = w.v[c] * invd[c];
+#pragma unroll
+    for (int c2 = 0; c2 < 6; ++c2) if (c2 > c) w.v[c2] = fma(-x.v[c], Ls[tri1_low(c2, c)], w.v[c2]);
+  }
+  return x;
 }
 // block column K of a panel, K a compile-time constant: every tile index below is static, so the 21 accumulator tiles stay
 // in registers (a run-time column index made the compiler address them through v_readlane / v_accvgpr chains: 75 us per panel)
@@ -924,8 +967,8 @@ __device__ __forceinline__ void tri1_step(const Tri1Ctx &X, d4_t (&C)[NJMAX * (N
   for (int h = 0; h < 2; ++h)
     if (X.rv[h] && X.rr[h] == K) store_row(&D6[6 * X.rho[h]], s[h]);
   __builtin_amdgcn_wave_barrier();
-  double Lk[21], invd[6];
-  ok_all = chol6_lds(D6, Lk, invd) && ok_all;
+  double Lk[15], invd[6];
+  ok_all = tri1_chol6(D6, lane, Lk, invd) && ok_all;
   __builtin_amdgcn_wave_barrier();
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -933,7 +976,7 @@ __device__ __forceinline__ void tri1_step(const Tri1Ctx &X, d4_t (&C)[NJMAX * (N
     const int i = lane + 64 * h;
     Row6 v = {{0, 0, 0, 0, 0, 0}};
     if (X.rv[h] && X.rr[h] >= K) {
-      v = trsm_row(s[h], Lk, invd);
+      v = tri1_trsm_row(s[h], Lk, invd);
       if (X.rr[h] == K) {
 #pragma unroll
         for (int c = 0; c < 6; ++c) v.v[c] = (c <= X.rho[h]) ? v.v[c] : 0.0;
@@ -1052,7 +1095,7 @@ __device__ __forceinline__ void tri1_body(const DevPlan &P, const double *__rest
     }
   }
 }
-__global__ __launch_bounds__(64) void k_panel_tri1(DevPlan P, const double *__restrict__ Hblk, double *__restrict__ Lv, int pn0,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_panel_tri1(DevPlan P, const double *__restrict__ Hblk, double *__restrict__ Lv, int pn0,
                                                    const double *__restrict__ lambda_p, int *__restrict__ fail_flag) {
   tri1_body(P, Hblk, Lv, pn0, lambda_p, fail_flag);
 }
