@@ -356,15 +356,13 @@ extern "C" int fgo_match_features_batch(int device, int64_t n_frames, const int6
   A.fx = P.fx; A.fy = P.fy; A.cx = P.cx; A.cy = P.cy;
   A.radius2 = P.radius_px * P.radius_px; A.max3d2 = P.max_dist_3d * P.max_dist_3d; A.r2 = P.ratio * P.ratio;
   A.ratio_test = P.ratio_test; A.cross_check = P.cross_check; A.max_desc = P.max_desc_dist2;
-  Events ev;
-  if (hipEventCreate(&ev.a) != hipSuccess || hipEventCreate(&ev.b) != hipSuccess) return FGO_ENUM;
-  (void)hipEventRecord(ev.a, 0);
+  KernelTimer timer;
+  if (!timer.start()) return FGO_ENUM;
   if (F > 0) hipLaunchKernelGGL(k_match_norms, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, 0, F, A.desc, A.xyz, S.ptr<int32_t>(h_nrm));
   hipLaunchKernelGGL(k_match, dim3((unsigned)n_pairs), dim3(FM_T), 0, 0, A);
-  (void)hipEventRecord(ev.b, 0);
+  timer.stop();
   if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return FGO_ENUM;
-  float ms = 0;
-  g_fm_kernel_ms = hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess ? (double)ms : 0.0;
+  g_fm_kernel_ms = timer.ms();
   if (int rc = S.download()) return rc;
 
   // ---- the host packs: the kept queries of a pair in ascending a, the counts of the pair

@@ -5,13 +5,12 @@
 //
 //   quantise  one lane per point: Q = llrint(x 2^20), the cell c = floor(Q / T) and its key, or the out-of-range mark.  Contraction
 //             is switched off for these lines; from there on everything is integer.
-//   sort      rocPRIM's radix sort of the (cell key, input index) pairs.  It is stable, so a cell's run is in ascending input index;
-//             the out-of-range mark is the largest key and sorts behind every cell.
-//   cells     the quantised coordinates are gathered into sorted order and the run heads are counted.  A cell's run is found by
-//             binary search of the sorted keys (map_cells_device.hpp, shared with kernels_map_normals.hip, as are the floor
-//             division and the key): neighbouring lanes look for neighbouring cells, so the upper levels of the search stay in cache.  An open-addressing table cell key -> start of the run (64-bit atomicCAS on the key, two slots per
-//             point) was built and measured as well: 5 % faster on a map of 44 000 points, 11 % slower on a sheet of 2 000 000,
-//             24 to 48 more bytes per point; it is not kept (the figures of both: profiles/NOTES.md).
+//   index     map_cell_index.hip, shared with kernels_map_normals.hip: the stable sort of the (cell key, input index) pairs and the
+//             gather of the quantised coordinates into sorted order, which counts the run heads.  A cell's run is found by binary
+//             search of the sorted keys (map_cells_device.hpp, as are the quantisation, the floor division and the key).  An
+//             open-addressing table cell key -> start of the run (64-bit atomicCAS on the key, two slots per point) was built and
+//             measured as well: 5 % faster on a map of 44 000 points, 11 % slower on a sheet of 2 000 000, 24 to 48 more bytes per
+//             point; it is not kept (the figures of both: profiles/NOTES.md).
 //   link      one lane per point in sorted order: it walks back over the points of its own cell that precede it and over the 13
 //             neighbour cells that precede its cell in key order -- every pair of points within reach is visited once -- applies
 //             dQ.dQ <= T^2 and unites the two points' sets in a lock-free union-find over the input indices.
@@ -30,7 +29,6 @@
 // Every barrier is outside every branch that is not uniform over the workgroup: the loops that hold one run over block-uniform
 // bounds.  The grids are capped and the kernels stride beyond that.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <stdint.h>
 #include <climits>
@@ -38,32 +36,27 @@
 #include <cstring>
 #include "../../include/fgo.h"
 #include "batch_call.hpp"
+#include "map_cell_index.hpp"
 #include "map_cells_device.hpp"
+#include "small_dense_device.hpp"
 
 namespace fgo {
 namespace {
 
-using dev::map_cell_key;
+using dev::map_cell_key, dev::MAP_QUANTA_PER_M, dev::MAP_CELL_BIAS, dev::MAP_CELL_EMPTY;      // |c_k| < 2^20; the key of an out-of-range point
 
 constexpr int MC_T = 256;                        // threads of a workgroup
-constexpr long long MC_IMAX = dev::MAP_CELL_BIAS; // |c_k| < 2^20
-constexpr unsigned long long MC_EMPTY = dev::MAP_CELL_EMPTY;      // the key of an out-of-range point: behind every cell in sorted order
 constexpr uint32_t MC_NONE = ~0u;                // no such cell
-constexpr unsigned MC_MAX_GRID = 1u << 20;       // workgroups of a launch; the kernels stride beyond that
 constexpr int MC_MAX_BINS = 8192;                // floor_span / floor_res <= 4096 gives at most 6145 bins (R = 1, S = 6144)
 constexpr unsigned MC_HIST_GRID = 1024;          // workgroups of the histogram: each flushes its bins once
 
 enum { MC_C_OOR, MC_C_CELLS, MC_C_CLUSTERS, MC_C_CLUSTERS_KEPT, MC_C_AFTER, MC_C_HMIN, MC_C_FLOOR_BIN, MC_C_FLOOR_CNT, MC_C_F, MC_C_KEPT,
        MC_C_COUNT };
 
-struct McArgs {
-  int64_t n;
+struct McArgs : dev::MapCellIndex {              // n, Q, sQ, key, skey, idx, sidx
   long long T, T2, R, S, C;
   int min_size, max_size, floor, axis, sign, nbins;
   const double *xyz;
-  long long *Q, *sQ;                             // n x 3: in input order, in sorted order
-  unsigned long long *key, *skey;                // in input order (what says "in range" from the sort on), sorted
-  uint32_t *idx, *sidx;
   int32_t *parent;
   uint32_t *size, *flag, *num, *pos, *bins;      // flag: is a root, then: is kept
   long long *cnt;
@@ -73,15 +66,7 @@ struct McArgs {
   double *xyz_out;
 };
 
-// counts the lanes that get here: the first of them adds their number, one atomic per wave and call.  (One atomicAdd of 1 per lane,
-// all on one address, measured 12 ns per POINT in a kernel that counted the kept points: nine tenths of the call.  The counts that
-// a scan ends on anyway -- clusters, kept points -- are read off the scan instead.)
-__device__ inline void mc_count(long long *cnt, int which) {
-  const unsigned long long m = __ballot(1);
-  if ((int)(threadIdx.x & 63) == __ffsll((long long)m) - 1)
-    atomicAdd(reinterpret_cast<unsigned long long *>(cnt + which), (unsigned long long)__popcll(m));
-}
-
+// (lanes are counted by dev::wave_count; the counts that a scan ends on anyway -- clusters, kept points -- are read off the scan)
 __global__ __launch_bounds__(MC_T) void k_mc_quantise(McArgs A) {
 #pragma clang fp contract(off)
   const int64_t stride = (int64_t)gridDim.x * MC_T;
@@ -90,34 +75,19 @@ __global__ __launch_bounds__(MC_T) void k_mc_quantise(McArgs A) {
     long long c[3] = {0, 0, 0};
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      const double y = A.xyz[3 * p + k] * 1048576.0;
-      long long Q = 0;
-      if (fabs(y) < 4611686018427387904.0) {                       // finite and below 2^62
-        Q = llrint(y);                                             // ties to even
+      long long Q;
+      if (dev::map_quantise(A.xyz[3 * p + k], 0x1p62, Q)) {               // 2^62: beyond any cell, and llrint is safe
         const long long q = dev::map_floor_div(Q, A.T);
-        if (q <= -MC_IMAX || q >= MC_IMAX) ok = false;
+        if (q <= -MAP_CELL_BIAS || q >= MAP_CELL_BIAS) ok = false;
         c[k] = q;
       } else ok = false;
       A.Q[3 * p + k] = Q;
     }
-    A.key[p] = ok ? map_cell_key(c[0] + MC_IMAX, c[1] + MC_IMAX, c[2] + MC_IMAX) : MC_EMPTY;
+    A.key[p] = ok ? map_cell_key(c[0] + MAP_CELL_BIAS, c[1] + MAP_CELL_BIAS, c[2] + MAP_CELL_BIAS) : MAP_CELL_EMPTY;
     A.idx[p] = (uint32_t)p;
     A.parent[p] = (int32_t)p;
     A.size[p] = 0;
-    if (!ok) mc_count(A.cnt, MC_C_OOR);
-  }
-}
-
-// Q in sorted order; the occupied cells are the run heads
-__global__ __launch_bounds__(MC_T) void k_mc_cells(McArgs A) {
-  const int64_t stride = (int64_t)gridDim.x * MC_T;
-  for (int64_t s = (int64_t)blockIdx.x * MC_T + threadIdx.x; s < A.n; s += stride) {
-    const unsigned long long key = A.skey[s];
-    if (key == MC_EMPTY) continue;
-    const int64_t p = A.sidx[s];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) A.sQ[3 * s + k] = A.Q[3 * p + k];
-    if (s == 0 || A.skey[s - 1] != key) mc_count(A.cnt, MC_C_CELLS);
+    if (!ok) dev::wave_count(A.cnt + MC_C_OOR);
   }
 }
 
@@ -157,7 +127,7 @@ __global__ __launch_bounds__(MC_T) void k_mc_link(McArgs A) {
   const int64_t stride = (int64_t)gridDim.x * MC_T;
   for (int64_t s = (int64_t)blockIdx.x * MC_T + threadIdx.x; s < A.n; s += stride) {
     const unsigned long long key = A.skey[s];
-    if (key == MC_EMPTY) continue;
+    if (key == MAP_CELL_EMPTY) continue;
     const long long q0 = A.sQ[3 * s], q1 = A.sQ[3 * s + 1], q2 = A.sQ[3 * s + 2];
     const int32_t p = (int32_t)A.sidx[s];
     auto visit = [&](int64_t j) {
@@ -165,10 +135,10 @@ __global__ __launch_bounds__(MC_T) void k_mc_link(McArgs A) {
       if (d0 * d0 + d1 * d1 + d2 * d2 <= A.T2) mc_unite(A.parent, p, (int32_t)A.sidx[j]);
     };
     for (int64_t j = s - 1; j >= 0 && A.skey[j] == key; --j) visit(j);         // its own cell: the points before it
-    const long long c[3] = {(long long)(key & 0x1fffff), (long long)((key >> 21) & 0x1fffff), (long long)(key >> 42)};      // c_k + 2^20
+    const long long c[3] = {dev::map_cell_coord(key, 0), dev::map_cell_coord(key, 1), dev::map_cell_coord(key, 2)};      // c_k + 2^20
     for (int t = 0; t < 13; ++t) {                                             // the neighbour cells before its own in key order
       const long long e[3] = {c[0] + t % 3 - 1, c[1] + (t / 3) % 3 - 1, c[2] + t / 9 - 1};
-      if (e[0] < 1 || e[1] < 1 || e[2] < 1 || e[0] >= 2 * MC_IMAX || e[1] >= 2 * MC_IMAX || e[2] >= 2 * MC_IMAX) continue;   // no such cell
+      if (e[0] < 1 || e[1] < 1 || e[2] < 1 || e[0] >= 2 * MAP_CELL_BIAS || e[1] >= 2 * MAP_CELL_BIAS || e[2] >= 2 * MAP_CELL_BIAS) continue;   // no such cell
       const unsigned long long nkey = map_cell_key(e[0], e[1], e[2]);
       const uint32_t j0 = mc_lookup(A, nkey);
       if (j0 == MC_NONE) continue;
@@ -182,7 +152,7 @@ __global__ __launch_bounds__(MC_T) void k_mc_flatten(McArgs A) {
   const int lane = threadIdx.x & 63;
   for (int64_t base = (int64_t)blockIdx.x * MC_T; base < A.n; base += (int64_t)gridDim.x * MC_T) {       // uniform over the workgroup
     const int64_t p = base + threadIdx.x;
-    bool todo = p < A.n && A.key[p] != MC_EMPTY;
+    bool todo = p < A.n && A.key[p] != MAP_CELL_EMPTY;
     int32_t r = -1;
     if (todo) {
       r = mc_find(A.parent, (int32_t)p);
@@ -207,10 +177,10 @@ __device__ inline bool mc_size_ok(const McArgs &A, uint32_t sz) {
 __global__ __launch_bounds__(MC_T) void k_mc_roots(McArgs A) {
   for (int64_t base = (int64_t)blockIdx.x * MC_T; base < A.n; base += (int64_t)gridDim.x * MC_T) {       // uniform over the workgroup
     const int64_t p = base + threadIdx.x;
-    const bool root = p < A.n && A.key[p] != MC_EMPTY && A.label[p] == (int32_t)p;
+    const bool root = p < A.n && A.key[p] != MAP_CELL_EMPTY && A.label[p] == (int32_t)p;
     if (p < A.n) A.flag[p] = root;
     unsigned long long kept = root && mc_size_ok(A, A.size[p]) ? A.size[p] : 0;
-    if (kept) mc_count(A.cnt, MC_C_CLUSTERS_KEPT);
+    if (kept) dev::wave_count(A.cnt + MC_C_CLUSTERS_KEPT);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o);
     if ((threadIdx.x & 63) == 0 && kept) atomicAdd(reinterpret_cast<unsigned long long *>(A.cnt + MC_C_AFTER), kept);
@@ -226,8 +196,8 @@ __global__ __launch_bounds__(MC_T) void k_mc_label(McArgs A) {
     long long h = LLONG_MAX;
     if (p < A.n) {
       bool keep = false;
-      if (p == A.n - 1) A.cnt[MC_C_CLUSTERS] = (long long)A.num[p] + (A.key[p] != MC_EMPTY && A.label[p] == (int32_t)p);
-      if (A.key[p] == MC_EMPTY) {
+      if (p == A.n - 1) A.cnt[MC_C_CLUSTERS] = (long long)A.num[p] + (A.key[p] != MAP_CELL_EMPTY && A.label[p] == (int32_t)p);
+      if (A.key[p] == MAP_CELL_EMPTY) {
         A.label[p] = -1;
         A.reason[p] = 1;
       } else {
@@ -309,7 +279,7 @@ __global__ __launch_bounds__(MC_T) void k_mc_mask(McArgs A) {
 __global__ __launch_bounds__(MC_T) void k_mc_compact(McArgs A) {
 #pragma clang fp contract(off)
   const bool floor = A.floor && A.cnt[MC_C_FLOOR_BIN] >= 0;
-  const double lift = (double)A.sign * ((double)A.cnt[MC_C_F] * (1.0 / 1048576.0));      // up_sign floor_height: exact
+  const double lift = (double)A.sign * ((double)A.cnt[MC_C_F] * (1.0 / MAP_QUANTA_PER_M));      // up_sign floor_height: exact
   const int64_t stride = (int64_t)gridDim.x * MC_T;
   for (int64_t p = (int64_t)blockIdx.x * MC_T + threadIdx.x; p < A.n; p += stride) {
     if (p == A.n - 1) A.cnt[MC_C_KEPT] = (long long)A.pos[p] + A.flag[p];      // where the scan ended
@@ -323,13 +293,6 @@ __global__ __launch_bounds__(MC_T) void k_mc_compact(McArgs A) {
     }
   }
 }
-
-unsigned grid_for(unsigned long long items, unsigned per_group) {
-  const unsigned long long g = (items + per_group - 1) / per_group;
-  return (unsigned)(g < 1 ? 1 : g > MC_MAX_GRID ? MC_MAX_GRID : g);
-}
-
-bool in_closed(double v, double lo, double hi) { return v >= lo && v <= hi; }      // false for a NaN
 
 double g_mc_kernel_ms = 0.0;
 
@@ -357,20 +320,20 @@ extern "C" int fgo_map_clean(int device, int64_t n_points, const double *xyz, co
   fgo_map_clean_params_default(&P);
   if (params) P = *params;
   if (!result || n_points < 0 || n_points >= (1ll << 30) || (n_points > 0 && !xyz)) return FGO_EINVAL;
-  if (!in_closed(P.tolerance, 1.0 / 1048576.0, 256.0)) return FGO_EINVAL;
+  if (!in_closed(P.tolerance, 1.0 / MAP_QUANTA_PER_M, 256.0)) return FGO_EINVAL;
   if (P.min_cluster_size < 1 || P.max_cluster_size < 0 || (P.max_cluster_size >= 1 && P.max_cluster_size < P.min_cluster_size)) return FGO_EINVAL;
   if (P.up_axis < 0 || P.up_axis > 2 || (P.up_sign != 1 && P.up_sign != -1) || (P.remove_floor != 0 && P.remove_floor != 1)) return FGO_EINVAL;
   McArgs A;
   std::memset(&A, 0, sizeof A);
   A.nbins = 1;
   if (P.remove_floor) {
-    if (!in_closed(P.floor_res, 1.0 / 1048576.0, 1024.0) || !in_closed(P.floor_span, 0.0, HUGE_VAL) || !(P.floor_span / P.floor_res <= 4096.0))
+    if (!in_closed(P.floor_res, 1.0 / MAP_QUANTA_PER_M, 1024.0) || !in_closed(P.floor_span, 0.0, HUGE_VAL) || !(P.floor_span / P.floor_res <= 4096.0))
       return FGO_EINVAL;
     if (!in_closed(P.floor_clearance, 0.0, HUGE_VAL) || P.floor_clearance == HUGE_VAL) return FGO_EINVAL;
-    A.R = llrint(P.floor_res * 1048576.0);
-    A.S = llrint(P.floor_span * 1048576.0);
-    const double c = P.floor_clearance * 1048576.0;
-    A.C = c < 4611686018427387904.0 ? llrint(c) : (1ll << 62);                  // no height reaches 2^49: beyond that every C acts alike
+    A.R = llrint(P.floor_res * MAP_QUANTA_PER_M);
+    A.S = llrint(P.floor_span * MAP_QUANTA_PER_M);
+    const double c = P.floor_clearance * MAP_QUANTA_PER_M;
+    A.C = c < 0x1p62 ? llrint(c) : (1ll << 62);                                // no height reaches 2^49: beyond that every C acts alike
     const long long nb = (A.S + A.R / 2) / A.R + 1;
     if (nb > MC_MAX_BINS) return FGO_EINVAL;                                    // the bounds above give at most 6145
     A.nbins = (int)nb;
@@ -382,18 +345,14 @@ extern "C" int fgo_map_clean(int device, int64_t n_points, const double *xyz, co
 
   const size_t n = (size_t)n_points;
   A.n = n_points;
-  A.T = llrint(P.tolerance * 1048576.0);
+  A.T = llrint(P.tolerance * MAP_QUANTA_PER_M);
   A.T2 = A.T * A.T;
   A.min_size = P.min_cluster_size; A.max_size = P.max_cluster_size;
   A.floor = P.remove_floor; A.axis = P.up_axis; A.sign = P.up_sign;
 
-  size_t sort_bytes = 0, scan_bytes = 0;
-  {
-    unsigned long long *no_key = nullptr;
-    uint32_t *no_val = nullptr;
-    if (rocprim::radix_sort_pairs(nullptr, sort_bytes, no_key, no_key, no_val, no_val, n, 0, 64, 0) != hipSuccess) return FGO_ENUM;
-    if (rocprim::exclusive_scan(nullptr, scan_bytes, no_val, no_val, 0u, n, rocprim::plus<uint32_t>(), 0) != hipSuccess) return FGO_ENUM;
-  }
+  size_t scan_bytes = 0;
+  uint32_t *no_val = nullptr;
+  if (rocprim::exclusive_scan(nullptr, scan_bytes, no_val, no_val, 0u, n, rocprim::plus<uint32_t>(), 0) != hipSuccess) return FGO_ENUM;
   long long cnt[MC_C_COUNT] = {0};
   cnt[MC_C_HMIN] = LLONG_MAX;
   cnt[MC_C_FLOOR_BIN] = -1;
@@ -402,51 +361,41 @@ extern "C" int fgo_map_clean(int device, int64_t n_points, const double *xyz, co
   const int h_label = S.out(label_out, n * sizeof(int32_t), true), h_reason = S.out(reason_out, n, true);
   const int h_csize = S.out(nullptr, n * sizeof(int32_t), true), h_index = S.out(nullptr, n * sizeof(int64_t), true);
   const int h_out = S.out(nullptr, 3 * n * sizeof(double), true);
-  const int h_Q = S.out(nullptr, 3 * n * sizeof(long long), true), h_sQ = S.out(nullptr, 3 * n * sizeof(long long), true);
-  const int h_key = S.out(nullptr, n * sizeof(unsigned long long), true), h_skey = S.out(nullptr, n * sizeof(unsigned long long), true);
-  const int h_idx = S.out(nullptr, n * sizeof(uint32_t), true), h_sidx = S.out(nullptr, n * sizeof(uint32_t), true);
+  MapCellStage index;                                              // the scans work in its scratch
+  if (int rc = index.reserve(S, n, scan_bytes)) return rc;
   const int h_parent = S.out(nullptr, n * sizeof(int32_t), true), h_size = S.out(nullptr, n * sizeof(uint32_t), true);
   const int h_flag = S.out(nullptr, n * sizeof(uint32_t), true), h_num = S.out(nullptr, n * sizeof(uint32_t), true);
   const int h_pos = S.out(nullptr, n * sizeof(uint32_t), true), h_bins = S.out(nullptr, MC_MAX_BINS * sizeof(uint32_t), true);
-  const int h_tmp = S.out(nullptr, sort_bytes > scan_bytes ? sort_bytes : scan_bytes, true);
   if (int rc = S.alloc()) return rc;
   if (int rc = S.upload()) return rc;
   A.xyz = S.ptr<double>(h_xyz); A.cnt = S.ptr<long long>(h_cnt);
   A.label = S.ptr<int32_t>(h_label); A.reason = S.ptr<uint8_t>(h_reason); A.csize = S.ptr<int32_t>(h_csize);
   A.index = S.ptr<int64_t>(h_index); A.xyz_out = S.ptr<double>(h_out);
-  A.Q = S.ptr<long long>(h_Q); A.sQ = S.ptr<long long>(h_sQ);
-  A.key = S.ptr<unsigned long long>(h_key); A.skey = S.ptr<unsigned long long>(h_skey);
-  A.idx = S.ptr<uint32_t>(h_idx); A.sidx = S.ptr<uint32_t>(h_sidx);
+  index.bind(S, A);
   A.parent = S.ptr<int32_t>(h_parent); A.size = S.ptr<uint32_t>(h_size);
   A.flag = S.ptr<uint32_t>(h_flag); A.num = S.ptr<uint32_t>(h_num); A.pos = S.ptr<uint32_t>(h_pos); A.bins = S.ptr<uint32_t>(h_bins);
-  void *tmp = S.ptr<void>(h_tmp);
 
-  Events ev;
-  if (hipEventCreate(&ev.a) != hipSuccess || hipEventCreate(&ev.b) != hipSuccess) return FGO_ENUM;
+  KernelTimer timer;
   const dim3 grid(grid_for(n, MC_T)), block(MC_T);
-  (void)hipEventRecord(ev.a, 0);
+  if (!timer.start()) return FGO_ENUM;
   if (hipMemsetAsync(A.bins, 0, MC_MAX_BINS * sizeof(uint32_t), 0) != hipSuccess) return FGO_ENUM;
   hipLaunchKernelGGL(k_mc_quantise, grid, block, 0, 0, A);
-  if (rocprim::radix_sort_pairs(tmp, sort_bytes, A.key, A.skey, A.idx, A.sidx, n, 0, 64, 0) != hipSuccess) return FGO_ENUM;
-  hipLaunchKernelGGL(k_mc_cells, grid, block, 0, 0, A);
+  if (int rc = index.build(A, A.cnt + MC_C_CELLS)) return rc;
   hipLaunchKernelGGL(k_mc_link, grid, block, 0, 0, A);
   hipLaunchKernelGGL(k_mc_flatten, grid, block, 0, 0, A);
   hipLaunchKernelGGL(k_mc_roots, grid, block, 0, 0, A);
-  if (rocprim::exclusive_scan(tmp, scan_bytes, A.flag, A.num, 0u, n, rocprim::plus<uint32_t>(), 0) != hipSuccess) return FGO_ENUM;
+  if (rocprim::exclusive_scan(index.scratch, scan_bytes, A.flag, A.num, 0u, n, rocprim::plus<uint32_t>(), 0) != hipSuccess) return FGO_ENUM;
   hipLaunchKernelGGL(k_mc_label, grid, block, 0, 0, A);
   if (P.remove_floor) {
-    const unsigned g = grid_for(n, MC_T);
-    hipLaunchKernelGGL(k_mc_hist, dim3(g < MC_HIST_GRID ? g : MC_HIST_GRID), block, 0, 0, A);
+    hipLaunchKernelGGL(k_mc_hist, dim3(grid.x < MC_HIST_GRID ? grid.x : MC_HIST_GRID), block, 0, 0, A);
     hipLaunchKernelGGL(k_mc_floor, dim3(1), block, 0, 0, A);
   }
   hipLaunchKernelGGL(k_mc_mask, grid, block, 0, 0, A);
-  if (rocprim::exclusive_scan(tmp, scan_bytes, A.flag, A.pos, 0u, n, rocprim::plus<uint32_t>(), 0) != hipSuccess) return FGO_ENUM;
+  if (rocprim::exclusive_scan(index.scratch, scan_bytes, A.flag, A.pos, 0u, n, rocprim::plus<uint32_t>(), 0) != hipSuccess) return FGO_ENUM;
   hipLaunchKernelGGL(k_mc_compact, grid, block, 0, 0, A);
-  (void)hipEventRecord(ev.b, 0);
+  timer.stop();
   if (hipMemcpy(cnt, A.cnt, sizeof cnt, hipMemcpyDeviceToHost) != hipSuccess || hipGetLastError() != hipSuccess) return FGO_ENUM;
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, ev.a, ev.b) != hipSuccess) ms = 0;
-  g_mc_kernel_ms = (double)ms;
+  g_mc_kernel_ms = timer.ms();
 
   result->n_points = n_points;
   result->n_out_of_range = cnt[MC_C_OOR];
@@ -458,7 +407,7 @@ extern "C" int fgo_map_clean(int device, int64_t n_points, const double *xyz, co
   result->n_kept = cnt[MC_C_KEPT];
   result->floor_bin = cnt[MC_C_FLOOR_BIN];
   result->floor_bin_points = cnt[MC_C_FLOOR_CNT];
-  result->floor_height = (double)cnt[MC_C_F] * (1.0 / 1048576.0);
+  result->floor_height = (double)cnt[MC_C_F] * (1.0 / MAP_QUANTA_PER_M);
   if (int rc = S.download()) return rc;                            // label and reason: n rows each
   // only the n_clusters sizes and the n_kept rows go back
   const size_t nc = (size_t)cnt[MC_C_CLUSTERS], nk = (size_t)cnt[MC_C_KEPT];

@@ -5,7 +5,7 @@
 //
 //   points    a point costs a handful of flops: every product, quotient and sum of its arithmetic is rounded on its own (contraction
 //             is switched off for those lines), the world coordinate is quantised to 2^-20 m and split into a voxel index and a
-//             remainder by integer floor division.  From there on everything is integer.
+//             remainder by integer floor division (map_cells_device.hpp, as is the key).  From there on everything is integer.
 //   table     ONE device-wide open-addressing hash table of 64-byte slots {key, n, S_x, S_y, S_z, C_0, C_1, C_2}, all 64-bit; the
 //             empty key is all-ones, probing is linear and wraps at the end.  A slot is claimed by a 64-bit atomicCAS on its key and
 //             summed into by 64-bit integer atomicAdd: the sums do not depend on the order of arrival.
@@ -19,13 +19,12 @@
 //             (<false, 1>): every point straight to the device-wide table.  The map does not depend on the form, nor on the order
 //             of the frames; the time does.  FGO_MAP_INSERT=frames / lds / plain picks the form of a call (development; the
 //             figures of all three: profiles/NOTES.md).
-//   pack      the occupied slots with n >= min_points are compacted into (key, slot) pairs; rocPRIM's device radix sort orders the
-//             pairs over the 63 key bits; the keys are distinct, so the order does not depend on how the compaction went.
+//   pack      the occupied slots with n >= min_points are compacted into (key, slot) pairs; the radix sort of map_cell_index.hip
+//             orders the pairs over the 63 key bits; the keys are distinct, so the order does not depend on how the compaction went.
 //   finalise  one thread per output row gathers centroid, colour, count and key through the sorted slots.
 // No floating-point atomics anywhere.  Every barrier is outside every branch that is not uniform over the workgroup: the tile loop
 // and its bounds are uniform, the point loop and the probe loops hold no barrier.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
 #include <stdint.h>
 #include <climits>
 #include <cmath>
@@ -34,18 +33,17 @@
 #include <vector>
 #include "../../include/fgo.h"
 #include "batch_call.hpp"
-#include "pose_host.hpp"
+#include "map_cell_index.hpp"
+#include "map_cells_device.hpp"
 
 namespace fgo {
 namespace {
 
+using dev::MAP_CELL_BIAS, dev::MAP_CELL_EMPTY, dev::MAP_QUANTA_PER_M;      // |i_k| < 2^20; the key of no voxel; 2^20
 constexpr int MF_T = 256;                        // threads of a workgroup
 constexpr int MF_TILE = 512;                     // sampled pixels of a tile
 constexpr int MF_LDS = 2 * MF_TILE;              // slots of the LDS table: at least twice the tile's points
 constexpr int MF_MAX_PIXELS = 1 << 24;
-constexpr long long MF_IMAX = 1ll << 20;         // |i_k| < 2^20
-constexpr unsigned long long MF_EMPTY = ~0ull;
-constexpr unsigned MF_MAX_GRID = 1u << 20;       // workgroups of a launch; the kernels stride beyond that
 
 struct MfSlot { unsigned long long key, n, s[3], c[3]; };      // 64 bytes
 
@@ -81,16 +79,14 @@ __device__ inline int mf_point(const MfArgs &A, const double *__restrict__ rt, i
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const double x = ((rt[3 * k] * p0 + rt[3 * k + 1] * p1) + rt[3 * k + 2] * z) + rt[9 + k];
-    const double y = x * 1048576.0;
-    if (!(fabs(y) < 4611686018427387904.0)) return 2;          // not finite, or beyond any index (2^62)
-    const long long Q = llrint(y);                             // ties to even
-    long long q = Q / A.L;
-    if (Q - q * A.L < 0) --q;                                  // floor division
-    if (q <= -MF_IMAX || q >= MF_IMAX) return 2;
+    long long Q;
+    if (!dev::map_quantise(x, 0x1p62, Q)) return 2;            // not finite, or beyond any index (2^62)
+    const long long q = dev::map_floor_div(Q, A.L);
+    if (q <= -MAP_CELL_BIAS || q >= MAP_CELL_BIAS) return 2;
     i[k] = q;
     r[k] = Q - q * A.L;
   }
-  key = ((unsigned long long)(i[2] + MF_IMAX) << 42) | ((unsigned long long)(i[1] + MF_IMAX) << 21) | (unsigned long long)(i[0] + MF_IMAX);
+  key = dev::map_cell_key(i[0] + MAP_CELL_BIAS, i[1] + MAP_CELL_BIAS, i[2] + MAP_CELL_BIAS);
   return 1;
 }
 
@@ -102,9 +98,9 @@ __device__ inline void mf_global_add(const MfArgs &A, unsigned long long key, un
     MfSlot *e = A.tab + h;
     unsigned long long prev = __atomic_load_n(&e->key, __ATOMIC_RELAXED);      // a key, once written, stays
     if (prev != key) {
-      if (prev != MF_EMPTY) continue;
-      prev = atomicCAS(&e->key, MF_EMPTY, key);
-      if (prev != MF_EMPTY && prev != key) continue;
+      if (prev != MAP_CELL_EMPTY) continue;
+      prev = atomicCAS(&e->key, MAP_CELL_EMPTY, key);
+      if (prev != MAP_CELL_EMPTY && prev != key) continue;
     }
     atomicAdd(&e->n, n);
 #pragma unroll
@@ -122,7 +118,7 @@ __global__ __launch_bounds__(256) void k_map_init(MfSlot *tab, unsigned long lon
   ulonglong2 *p = reinterpret_cast<ulonglong2 *>(tab);                         // four 16-byte pieces per slot; the first holds the key
   const unsigned long long n = 4 * n_slots, stride = (unsigned long long)gridDim.x * blockDim.x;
   for (unsigned long long k = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride)
-    p[k] = make_ulonglong2((k & 3) == 0 ? MF_EMPTY : 0ull, 0ull);
+    p[k] = make_ulonglong2((k & 3) == 0 ? MAP_CELL_EMPTY : 0ull, 0ull);
 }
 
 // A tile is PX = MF_TILE / FR consecutive sampled pixels of FR consecutive frames: FR = 1 is a run of one frame, FR > 1 the same run
@@ -141,7 +137,7 @@ __global__ __launch_bounds__(MF_T) void k_map_insert(MfArgs A) {
     const int64_t s0 = (b - g * A.tiles) * PX;
     if (AGG) {
       for (int s = tid; s < MF_LDS; s += MF_T) {
-        s_key[s] = MF_EMPTY;
+        s_key[s] = MAP_CELL_EMPTY;
         s_sum[3 * s] = s_sum[3 * s + 1] = s_sum[3 * s + 2] = 0;
         s_cnt[4 * s] = s_cnt[4 * s + 1] = s_cnt[4 * s + 2] = s_cnt[4 * s + 3] = 0;
       }
@@ -167,8 +163,8 @@ __global__ __launch_bounds__(MF_T) void k_map_insert(MfArgs A) {
       if (AGG) {
         unsigned int h = (unsigned int)(mf_hash(key) >> 32) & (MF_LDS - 1);
         for (;;) {                                                             // ends: the tile has at most MF_LDS / 2 keys
-          const unsigned long long prev = atomicCAS(&s_key[h], MF_EMPTY, key);
-          if (prev == MF_EMPTY || prev == key) break;
+          const unsigned long long prev = atomicCAS(&s_key[h], MAP_CELL_EMPTY, key);
+          if (prev == MAP_CELL_EMPTY || prev == key) break;
           h = (h + 1) & (MF_LDS - 1);
         }
         atomicAdd(&s_cnt[4 * h], 1u);
@@ -186,7 +182,7 @@ __global__ __launch_bounds__(MF_T) void k_map_insert(MfArgs A) {
     if (AGG) {
       for (int s = tid; s < MF_LDS; s += MF_T) {
         const unsigned long long key = s_key[s];
-        if (key == MF_EMPTY) continue;
+        if (key == MAP_CELL_EMPTY) continue;
         const unsigned long long s3[3] = {s_sum[3 * s], s_sum[3 * s + 1], s_sum[3 * s + 2]};
         const unsigned long long c3[3] = {s_cnt[4 * s + 1], s_cnt[4 * s + 2], s_cnt[4 * s + 3]};
         mf_global_add(A, key, s_cnt[4 * s], s3, c3);
@@ -205,7 +201,7 @@ __global__ __launch_bounds__(256) void k_map_pack(const MfSlot *__restrict__ tab
   const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
   for (unsigned long long s = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; s < n_slots; s += stride) {
     const unsigned long long key = tab[s].key;
-    if (key == MF_EMPTY) continue;
+    if (key == MAP_CELL_EMPTY) continue;
     if (tab[s].n >= min_points) {
       const unsigned long long at = atomicAdd(&counters[MF_C_VOXELS], 1ull);
       pk[at] = key;
@@ -221,11 +217,10 @@ __global__ __launch_bounds__(256) void k_map_finalise(const MfSlot *__restrict__
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += stride) {
     const MfSlot e = tab[slot[j]];
-    const long long i[3] = {(long long)(e.key & 0x1fffff) - MF_IMAX, (long long)((e.key >> 21) & 0x1fffff) - MF_IMAX,
-                            (long long)(e.key >> 42) - MF_IMAX};
     const double n = (double)e.n;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) xyz[3 * j + k] = ((double)(i[k] * L) + (double)e.s[k] / n) * (1.0 / 1048576.0);
+    for (int k = 0; k < 3; ++k)
+      xyz[3 * j + k] = ((double)((dev::map_cell_coord(e.key, k) - MAP_CELL_BIAS) * L) + (double)e.s[k] / n) * (1.0 / MAP_QUANTA_PER_M);
     for (int k = 0; k < ch; ++k) color[j * ch + k] = (uint8_t)((2 * e.c[k] + e.n) / (2 * e.n));
     count[j] = (int32_t)e.n;
     key_out[j] = (int64_t)e.key;
@@ -241,11 +236,6 @@ int insert_form() {
   if (e && std::strcmp(e, "lds") == 0) return MF_LDS_FRAME;
   if (e && std::strcmp(e, "frames") == 0) return MF_LDS_GROUP;
   return MF_LDS_GROUP;
-}
-
-unsigned grid_for(unsigned long long items, unsigned per_group) {
-  const unsigned long long g = (items + per_group - 1) / per_group;
-  return (unsigned)(g < 1 ? 1 : g > MF_MAX_GRID ? MF_MAX_GRID : g);
 }
 
 double g_mf_kernel_ms = 0.0;
@@ -279,9 +269,8 @@ extern "C" int fgo_map_fuse_batch(int device, int64_t n_frames, int width, int h
   if (!result || n_frames < 0 || max_voxels < 0) return FGO_EINVAL;
   if (width < 1 || height < 1 || (int64_t)width * height > MF_MAX_PIXELS) return FGO_EINVAL;
   if (channels != 0 && channels != 1 && channels != 3) return FGO_EINVAL;
-  if (!(P.fx > 0) || !(P.fy > 0) || !(P.z_scale > 0) || !(fabs(P.cx) < HUGE_VAL) || !(fabs(P.cy) < HUGE_VAL)) return FGO_EINVAL;
-  if (!(P.fx < HUGE_VAL) || !(P.fy < HUGE_VAL) || !(P.z_scale < HUGE_VAL) || !(P.z_min < P.z_max)) return FGO_EINVAL;
-  if (P.skip < 1 || P.min_points < 1 || !(P.leaf >= 1.0 / 1048576.0 && P.leaf <= 1024.0)) return FGO_EINVAL;
+  if (!pinhole_ok(P.fx, P.fy, P.cx, P.cy, P.z_scale) || !(P.z_min < P.z_max)) return FGO_EINVAL;
+  if (P.skip < 1 || P.min_points < 1 || !in_closed(P.leaf, 1.0 / MAP_QUANTA_PER_M, 1024.0)) return FGO_EINVAL;
   if (P.table_log2 != 0 && (P.table_log2 < 4 || P.table_log2 > 32)) return FGO_EINVAL;
   int su = P.rect[0], sv = P.rect[1], eu = P.rect[2], ev = P.rect[3];
   if (su == 0 && sv == 0 && eu == 0 && ev == 0) { eu = width; ev = height; }
@@ -292,18 +281,15 @@ extern "C" int fgo_map_fuse_batch(int device, int64_t n_frames, int width, int h
   std::memset(result, 0, sizeof *result);
   if (n_frames == 0) return FGO_OK;
   if (!depth || !pose_w7 || (color == nullptr) != (channels == 0) || (max_voxels > 0 && !xyz_out)) return FGO_EINVAL;
-  if (extrinsic7 && !quat_ok(extrinsic7 + 3)) return FGO_EINVAL;
-  for (int64_t f = 0; f < n_frames; ++f)
-    if (!quat_ok(pose_w7 + 7 * f + 3)) return FGO_EINVAL;
+  std::vector<double> rt;
+  if (!poses_rt(pose_w7, n_frames, extrinsic7, rt)) return FGO_EINVAL;
   if (int rc = select_device(device)) return rc;
 
   int T = P.table_log2;
   if (T == 0)
     for (T = 4; (1ll << T) < 2 * n_sampled; ++T) {}
   const unsigned long long n_slots = 1ull << T;
-  const long long L = llrint(P.leaf * 1048576.0);
-  std::vector<double> rt(12 * (size_t)n_frames);
-  for (int64_t f = 0; f < n_frames; ++f) pose_rt(pose_w7 + 7 * f, extrinsic7, rt.data() + 12 * f);
+  const long long L = llrint(P.leaf * MAP_QUANTA_PER_M);
   result->table_log2 = T;
   result->n_sampled = n_sampled;
 
@@ -326,11 +312,8 @@ extern "C" int fgo_map_fuse_batch(int device, int64_t n_frames, int width, int h
   A.depth = S.ptr<uint16_t>(h_depth); A.color = S.ptr<uint8_t>(h_color); A.rt = S.ptr<double>(h_rt);
   A.fx = P.fx; A.fy = P.fy; A.cx = P.cx; A.cy = P.cy; A.z_scale = P.z_scale; A.z_min = P.z_min; A.z_max = P.z_max;
   A.L = L; A.tab = S.ptr<MfSlot>(h_tab); A.mask = n_slots - 1; A.counters = d_cnt;
-  Events ev1, ev2;
-  if (hipEventCreate(&ev1.a) != hipSuccess || hipEventCreate(&ev1.b) != hipSuccess || hipEventCreate(&ev2.a) != hipSuccess ||
-      hipEventCreate(&ev2.b) != hipSuccess)
-    return FGO_ENUM;
-  (void)hipEventRecord(ev1.a, 0);
+  KernelTimer timer1, timer2;                    // the table up to the pack; the sort and the output rows
+  if (!timer1.start()) return FGO_ENUM;
   hipLaunchKernelGGL(k_map_init, dim3(grid_for(4 * n_slots, 256 * 8)), dim3(256), 0, 0, A.tab, n_slots);
   const dim3 grid(grid_for((unsigned long long)A.n_tiles, 1));
   if (form == MF_LDS_GROUP) hipLaunchKernelGGL((k_map_insert<true, MF_GROUP>), grid, dim3(MF_T), 0, 0, A);
@@ -338,13 +321,11 @@ extern "C" int fgo_map_fuse_batch(int device, int64_t n_frames, int width, int h
   else hipLaunchKernelGGL((k_map_insert<false, 1>), grid, dim3(MF_T), 0, 0, A);
   hipLaunchKernelGGL(k_map_pack, dim3(grid_for(n_slots, 256 * 4)), dim3(256), 0, 0, A.tab, n_slots, (unsigned long long)P.min_points, d_cnt,
                      S.ptr<unsigned long long>(h_pk), S.ptr<uint32_t>(h_ps));
-  (void)hipEventRecord(ev1.b, 0);
+  timer1.stop();
   std::vector<unsigned long long> cnt(n_count);
   if (hipMemcpy(cnt.data(), d_cnt, n_count * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess || hipGetLastError() != hipSuccess)
     return FGO_ENUM;
-  float ms1 = 0, ms2 = 0;
-  if (hipEventElapsedTime(&ms1, ev1.a, ev1.b) != hipSuccess) ms1 = 0;
-  g_mf_kernel_ms = (double)ms1;
+  g_mf_kernel_ms = timer1.ms();
   for (size_t f = 0; f < nf; ++f) {
     result->n_valid += (int64_t)cnt[MF_C_FRAMES + f];
     if (frame_points_out) frame_points_out[f] = (int64_t)cnt[MF_C_FRAMES + f];
@@ -363,23 +344,21 @@ extern "C" int fgo_map_fuse_batch(int device, int64_t n_frames, int width, int h
 
   // the sorted pairs, the sort's scratch and the m output rows: sized now that the number of voxels is known
   size_t tmp_bytes = 0;
-  unsigned long long *pk = S.ptr<unsigned long long>(h_pk), *no_key = nullptr;
-  uint32_t *ps = S.ptr<uint32_t>(h_ps), *no_slot = nullptr;
-  if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, pk, no_key, ps, no_slot, nv, 0, 63, 0) != hipSuccess) return FGO_ENUM;
+  if (int rc = map_sort_pairs_bytes(nv, 63, tmp_bytes)) return rc;
   Arena B;
   const size_t o_tmp = B.reserve(tmp_bytes), o_sk = B.reserve(nv * sizeof(unsigned long long)), o_ss = B.reserve(nv * sizeof(uint32_t));
   const size_t o_xyz = B.reserve(3 * m * sizeof(double)), o_col = B.reserve(m * (size_t)channels), o_n = B.reserve(m * sizeof(int32_t));
   const size_t o_key = B.reserve(m * sizeof(int64_t));
   if (B.alloc() != hipSuccess) return FGO_ENOMEM;
-  (void)hipEventRecord(ev2.a, 0);
-  if (rocprim::radix_sort_pairs(B.at<void>(o_tmp), tmp_bytes, pk, B.at<unsigned long long>(o_sk), ps, B.at<uint32_t>(o_ss), nv, 0, 63, 0) !=
-      hipSuccess)
-    return FGO_ENUM;
+  if (!timer2.start()) return FGO_ENUM;
+  if (int rc = map_sort_pairs(B.at<void>(o_tmp), tmp_bytes, S.ptr<unsigned long long>(h_pk), B.at<unsigned long long>(o_sk), S.ptr<uint32_t>(h_ps),
+                              B.at<uint32_t>(o_ss), nv, 63))
+    return rc;
   hipLaunchKernelGGL(k_map_finalise, dim3(grid_for(m, 256)), dim3(256), 0, 0, A.tab, B.at<uint32_t>(o_ss), (int64_t)m, L, channels,
                      B.at<double>(o_xyz), B.at<uint8_t>(o_col), B.at<int32_t>(o_n), B.at<int64_t>(o_key));
-  (void)hipEventRecord(ev2.b, 0);
+  timer2.stop();
   if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return FGO_ENUM;
-  if (hipEventElapsedTime(&ms2, ev2.a, ev2.b) == hipSuccess) g_mf_kernel_ms += (double)ms2;
+  g_mf_kernel_ms += timer2.ms();
   // only the m rows go back
   void *const host[4] = {xyz_out, channels ? color_out : nullptr, count_out, key_out};
   const size_t off[4] = {o_xyz, o_col, o_n, o_key}, bytes[4] = {3 * m * sizeof(double), m * (size_t)channels, m * sizeof(int32_t), m * sizeof(int64_t)};

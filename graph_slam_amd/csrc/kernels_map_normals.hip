@@ -6,9 +6,8 @@
 //
 //   quantise  one lane per point: Q = llrint(x 2^20), the range test |Q_k| < 2^34, the cell c = floor(Q / T_cell) and its key, or the
 //             out-of-range mark and that point's outputs (status 1, NaN, no neighbours).
-//   sort      rocPRIM's radix sort of the (cell key, input index) pairs, as in kernels_map_clean.hip.  It is stable, so a cell's run
-//             is in ascending input index; the out-of-range mark sorts behind every cell.
-//   gather    Q in sorted order; the run heads are the occupied cells.
+//   index     map_cell_index.hip, shared with kernels_map_clean.hip: the stable sort of the (cell key, input index) pairs, so a
+//             cell's run is in ascending input index, and the gather of Q into sorted order; the run heads are the occupied cells.
 //   search    one lane per point in SORTED order, so that the lanes of a wave read the same runs.  The cells are visited in rings
 //             (Chebyshev shells) around the point's own cell.  The x coordinate is the low field of the key, so the cells of one
 //             (y, z) row of a shell are one stretch of the sorted keys: one binary search per row, two for a row of which only the
@@ -28,37 +27,34 @@
 // capped and the kernels stride beyond that.
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
 #include <stdint.h>
 #include <climits>
 #include <cmath>
 #include <cstring>
 #include "../../include/fgo.h"
 #include "batch_call.hpp"
+#include "map_cell_index.hpp"
 #include "map_cells_device.hpp"
 #include "small_dense_device.hpp"
 
 namespace fgo {
 namespace {
 
+using dev::MAP_QUANTA_PER_M;
+
 constexpr int MN_T = 256;                        // threads of a workgroup; the search runs with 256, 128 or 64
 constexpr int MN_K_MAX = 64;
 constexpr size_t MN_LDS = 65536;                 // what the candidate lists of a workgroup may take
 constexpr long long MN_QMAX = 1ll << 34;         // |Q_k| < 2^34
-constexpr unsigned MN_MAX_GRID = 1u << 20;       // workgroups of a launch; the kernels stride beyond that
 constexpr int MN_SWEEPS = 8;                     // cyclic Jacobi sweeps (quadratic convergence: 4 - 5 reach rounding)
 
 enum { MN_C_OOR, MN_C_CELLS, MN_C_VALID, MN_C_FEW, MN_C_DEGENERATE, MN_C_COUNT };
 
-struct MnArgs {
-  int64_t n;
+struct MnArgs : dev::MapCellIndex {              // n, Q, sQ, key, skey, idx, sidx
   int k;
   long long T, R, R2;                            // the cell, the radius and its square, in quanta
   double view[3];
   const double *xyz;
-  long long *Q, *sQ;                             // n x 3: in input order, in sorted order
-  unsigned long long *key, *skey;
-  uint32_t *idx, *sidx;
   long long *cnt;
   double *normal, *curvature, *eig;              // eig may be NULL
   int32_t *nn;
@@ -66,13 +62,6 @@ struct MnArgs {
   int32_t *neighbour;                            // n x k, may be NULL
   int64_t *dist2, *scatter;                      // n x k, n x 6, may be NULL
 };
-
-// counts the lanes that get here: one atomic per wave and call (see kernels_map_clean.hip)
-__device__ inline void mn_count(long long *cnt, int which) {
-  const unsigned long long m = __ballot(1);
-  if ((int)(threadIdx.x & 63) == __ffsll((long long)m) - 1)
-    atomicAdd(reinterpret_cast<unsigned long long *>(cnt + which), (unsigned long long)__popcll(m));
-}
 
 // what a point without a fit gets: NaN for every floating output
 __device__ inline void mn_no_fit(const MnArgs &A, int64_t p, int status) {
@@ -93,10 +82,8 @@ __global__ __launch_bounds__(MN_T) void k_mn_quantise(MnArgs A) {
     long long e[3] = {0, 0, 0};
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const double y = A.xyz[3 * p + c] * dev::MAP_QUANTA_PER_M;
-      long long Q = 0;
-      if (fabs(y) < 34359738368.0) {                               // finite and below 2^35: llrint is safe
-        Q = llrint(y);                                             // ties to even
+      long long Q;
+      if (dev::map_quantise(A.xyz[3 * p + c], 0x1p35, Q)) {               // 2^35: beyond the range, and llrint is safe
         if (Q <= -MN_QMAX || Q >= MN_QMAX) ok = false;
         e[c] = dev::map_floor_div(Q, A.T) + dev::MAP_CELL_BIAS;    // in [0, 2^21) when in range: T >= 2^14
       } else ok = false;
@@ -113,27 +100,14 @@ __global__ __launch_bounds__(MN_T) void k_mn_quantise(MnArgs A) {
       }
       if (A.scatter)
         for (int c = 0; c < 6; ++c) A.scatter[6 * p + c] = 0;
-      mn_count(A.cnt, MN_C_OOR);
+      dev::wave_count(A.cnt + MN_C_OOR);
     }
-  }
-}
-
-// Q in sorted order; the occupied cells are the run heads
-__global__ __launch_bounds__(MN_T) void k_mn_gather(MnArgs A) {
-  const int64_t stride = (int64_t)gridDim.x * MN_T;
-  for (int64_t s = (int64_t)blockIdx.x * MN_T + threadIdx.x; s < A.n; s += stride) {
-    const unsigned long long key = A.skey[s];
-    if (key == dev::MAP_CELL_EMPTY) continue;
-    const int64_t p = A.sidx[s];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) A.sQ[3 * s + c] = A.Q[3 * p + c];
-    if (s == 0 || A.skey[s - 1] != key) mn_count(A.cnt, MN_C_CELLS);
   }
 }
 
 // the eigen-decomposition of the scatter matrix, the normal, its orientation and the curvature of one valid point
 __device__ inline void mn_fit(const MnArgs &A, int64_t p, int m, const long long M[6], const long long q[3]) {
-  const double den = (double)((long long)m * m) * 1099511627776.0;           // m^2 2^40: exact
+  const double den = (double)((long long)m * m) * (MAP_QUANTA_PER_M * MAP_QUANTA_PER_M);      // m^2 2^40, quanta^2 to m^2: exact
   const double xx = (double)M[0] / den, xy = (double)M[1] / den, xz = (double)M[2] / den;
   const double yy = (double)M[3] / den, yz = (double)M[4] / den, zz = (double)M[5] / den;
   double a[9] = {xx, xy, xz, xy, yy, yz, xz, yz, zz};
@@ -155,8 +129,8 @@ __device__ inline void mn_fit(const MnArgs &A, int64_t p, int m, const long long
   order(0, 1); order(1, 2); order(0, 1);
   const double len = sqrt((e[0][0] * e[0][0] + e[0][1] * e[0][1]) + e[0][2] * e[0][2]);
   double nx = e[0][0] / len, ny = e[0][1] / len, nz = e[0][2] / len;
-  const double d0 = A.view[0] - (double)q[0] * (1.0 / dev::MAP_QUANTA_PER_M), d1 = A.view[1] - (double)q[1] * (1.0 / dev::MAP_QUANTA_PER_M),
-               d2 = A.view[2] - (double)q[2] * (1.0 / dev::MAP_QUANTA_PER_M);
+  const double d0 = A.view[0] - (double)q[0] * (1.0 / MAP_QUANTA_PER_M), d1 = A.view[1] - (double)q[1] * (1.0 / MAP_QUANTA_PER_M),
+               d2 = A.view[2] - (double)q[2] * (1.0 / MAP_QUANTA_PER_M);
   const double dot = (nx * d0 + ny * d1) + nz * d2;
   bool flip = dot < 0;
   if (dot == 0) flip = nx != 0 ? nx < 0 : ny != 0 ? ny < 0 : nz < 0;         // the first non-zero component positive
@@ -181,7 +155,7 @@ __global__ __launch_bounds__(MN_T) void k_mn_search(MnArgs A) {
     if (key == dev::MAP_CELL_EMPTY) continue;
     const long long q[3] = {A.sQ[3 * s], A.sQ[3 * s + 1], A.sQ[3 * s + 2]};
     const int64_t p = A.sidx[s];
-    const long long c[3] = {(long long)(key & 0x1fffff), (long long)((key >> 21) & 0x1fffff), (long long)(key >> 42)};      // biased
+    const long long c[3] = {dev::map_cell_coord(key, 0), dev::map_cell_coord(key, 1), dev::map_cell_coord(key, 2)};      // biased
     long long gmin = LLONG_MAX;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -254,23 +228,16 @@ __global__ __launch_bounds__(MN_T) void k_mn_search(MnArgs A) {
       for (int a = 0; a < 6; ++a) A.scatter[6 * p + a] = M[a];
     if (cnt < 3) {
       mn_no_fit(A, p, 2);
-      mn_count(A.cnt, MN_C_FEW);
+      dev::wave_count(A.cnt + MN_C_FEW);
     } else if ((M[0] | M[1] | M[2] | M[3] | M[4] | M[5]) == 0) {
       mn_no_fit(A, p, 3);
-      mn_count(A.cnt, MN_C_DEGENERATE);
+      dev::wave_count(A.cnt + MN_C_DEGENERATE);
     } else {
       mn_fit(A, p, cnt, M, q);
-      mn_count(A.cnt, MN_C_VALID);
+      dev::wave_count(A.cnt + MN_C_VALID);
     }
   }
 }
-
-unsigned mn_grid_for(unsigned long long items, unsigned per_group) {
-  const unsigned long long g = (items + per_group - 1) / per_group;
-  return (unsigned)(g < 1 ? 1 : g > MN_MAX_GRID ? MN_MAX_GRID : g);
-}
-
-bool mn_in_closed(double v, double lo, double hi) { return v >= lo && v <= hi; }      // false for a NaN
 
 double g_mn_kernel_ms = 0.0;
 
@@ -298,7 +265,7 @@ extern "C" int fgo_map_normals(int device, int64_t n_points, const double *xyz, 
   if (!result || n_points < 0 || n_points >= (1ll << 30) || (n_points > 0 && !xyz)) return FGO_EINVAL;
   if (n_points > 0 && (!normal_out || !curvature_out || !n_neighbours_out || !status_out)) return FGO_EINVAL;
   if (P.k < 3 || P.k > MN_K_MAX) return FGO_EINVAL;
-  if (!mn_in_closed(P.max_radius, 1.0 / 1048576.0, 16.0) || !mn_in_closed(P.cell, 1.0 / 64.0, 16.0)) return FGO_EINVAL;
+  if (!in_closed(P.max_radius, 1.0 / MAP_QUANTA_PER_M, 16.0) || !in_closed(P.cell, 1.0 / 64.0, 16.0)) return FGO_EINVAL;
   if (!(P.max_radius / P.cell <= 16.0)) return FGO_EINVAL;
   for (int c = 0; c < 3; ++c)
     if (!std::isfinite(P.viewpoint[c])) return FGO_EINVAL;
@@ -311,19 +278,13 @@ extern "C" int fgo_map_normals(int device, int64_t n_points, const double *xyz, 
   std::memset(&A, 0, sizeof A);
   A.n = n_points;
   A.k = P.k;
-  A.T = llrint(P.cell * 1048576.0);
-  A.R = llrint(P.max_radius * 1048576.0);
+  A.T = llrint(P.cell * MAP_QUANTA_PER_M);
+  A.R = llrint(P.max_radius * MAP_QUANTA_PER_M);
   A.R2 = A.R * A.R;
   for (int c = 0; c < 3; ++c) A.view[c] = P.viewpoint[c];
   unsigned W = MN_T;                                                          // the search's workgroup: its lists fit MN_LDS
   while (W > 64 && k * W * 12 > MN_LDS) W /= 2;
 
-  size_t sort_bytes = 0;
-  {
-    unsigned long long *no_key = nullptr;
-    uint32_t *no_val = nullptr;
-    if (rocprim::radix_sort_pairs(nullptr, sort_bytes, no_key, no_key, no_val, no_val, n, 0, 64, 0) != hipSuccess) return FGO_ENUM;
-  }
   long long cnt[MN_C_COUNT] = {0};
   Staged S;
   const int h_xyz = S.in(xyz, 3 * n * sizeof(double)), h_cnt = S.in(cnt, sizeof cnt);
@@ -332,34 +293,24 @@ extern "C" int fgo_map_normals(int device, int64_t n_points, const double *xyz, 
   const int h_nn = S.out(n_neighbours_out, n * sizeof(int32_t)), h_status = S.out(status_out, n);
   const int h_nb = S.out(neighbour_out, n * k * sizeof(int32_t)), h_d2 = S.out(dist2_out, n * k * sizeof(int64_t));
   const int h_sc = S.out(scatter_out, 6 * n * sizeof(int64_t));
-  const int h_Q = S.out(nullptr, 3 * n * sizeof(long long), true), h_sQ = S.out(nullptr, 3 * n * sizeof(long long), true);
-  const int h_key = S.out(nullptr, n * sizeof(unsigned long long), true), h_skey = S.out(nullptr, n * sizeof(unsigned long long), true);
-  const int h_idx = S.out(nullptr, n * sizeof(uint32_t), true), h_sidx = S.out(nullptr, n * sizeof(uint32_t), true);
-  const int h_tmp = S.out(nullptr, sort_bytes, true);
+  MapCellStage index;
+  if (int rc = index.reserve(S, n)) return rc;
   if (int rc = S.alloc()) return rc;
   if (int rc = S.upload()) return rc;
   A.xyz = S.ptr<double>(h_xyz); A.cnt = S.ptr<long long>(h_cnt);
   A.normal = S.ptr<double>(h_normal); A.curvature = S.ptr<double>(h_curv); A.eig = S.ptr<double>(h_eig);
   A.nn = S.ptr<int32_t>(h_nn); A.status = S.ptr<uint8_t>(h_status);
   A.neighbour = S.ptr<int32_t>(h_nb); A.dist2 = S.ptr<int64_t>(h_d2); A.scatter = S.ptr<int64_t>(h_sc);
-  A.Q = S.ptr<long long>(h_Q); A.sQ = S.ptr<long long>(h_sQ);
-  A.key = S.ptr<unsigned long long>(h_key); A.skey = S.ptr<unsigned long long>(h_skey);
-  A.idx = S.ptr<uint32_t>(h_idx); A.sidx = S.ptr<uint32_t>(h_sidx);
-  void *tmp = S.ptr<void>(h_tmp);
+  index.bind(S, A);
 
-  Events ev;
-  if (hipEventCreate(&ev.a) != hipSuccess || hipEventCreate(&ev.b) != hipSuccess) return FGO_ENUM;
-  const dim3 grid(mn_grid_for(n, MN_T)), block(MN_T);
-  (void)hipEventRecord(ev.a, 0);
-  hipLaunchKernelGGL(k_mn_quantise, grid, block, 0, 0, A);
-  if (rocprim::radix_sort_pairs(tmp, sort_bytes, A.key, A.skey, A.idx, A.sidx, n, 0, 64, 0) != hipSuccess) return FGO_ENUM;
-  hipLaunchKernelGGL(k_mn_gather, grid, block, 0, 0, A);
-  hipLaunchKernelGGL(k_mn_search, dim3(mn_grid_for(n, W)), dim3(W), k * W * 12, 0, A);
-  (void)hipEventRecord(ev.b, 0);
+  KernelTimer timer;
+  if (!timer.start()) return FGO_ENUM;
+  hipLaunchKernelGGL(k_mn_quantise, dim3(grid_for(n, MN_T)), dim3(MN_T), 0, 0, A);
+  if (int rc = index.build(A, A.cnt + MN_C_CELLS)) return rc;
+  hipLaunchKernelGGL(k_mn_search, dim3(grid_for(n, W)), dim3(W), k * W * 12, 0, A);
+  timer.stop();
   if (hipMemcpy(cnt, A.cnt, sizeof cnt, hipMemcpyDeviceToHost) != hipSuccess || hipGetLastError() != hipSuccess) return FGO_ENUM;
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, ev.a, ev.b) != hipSuccess) ms = 0;
-  g_mn_kernel_ms = (double)ms;
+  g_mn_kernel_ms = timer.ms();
 
   result->n_points = n_points;
   result->n_out_of_range = cnt[MN_C_OOR];

@@ -25,6 +25,7 @@
 //             strip: in the tiles form only the workgroup of strip 0 (and for n_nonfinite of view 0) counts them.
 // The 12 numbers of a view are uniform over the workgroup.  No floating-point atomics anywhere.  Every barrier is outside every
 // branch that is not uniform over the workgroup: the tile loops and their bounds are uniform, the point loop holds no barrier.
+// The quantum is the map's (map_cells_device.hpp); the host side shares the checks of camera and poses with the fusion (batch_call.hpp).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <climits>
@@ -34,19 +35,19 @@
 #include <vector>
 #include "../../include/fgo.h"
 #include "batch_call.hpp"
-#include "pose_host.hpp"
+#include "map_cells_device.hpp"
 
 #pragma clang fp contract(off)
 
 namespace fgo {
 namespace {
 
+using dev::MAP_QUANTA_PER_M;                     // depths are quantised to the map's quantum, 2^-20 m
 constexpr int MR_T = 256;                        // threads of a workgroup
 constexpr int MR_STRIP = 8192;                   // pixels of a strip: 64 KiB of 64-bit words
 constexpr int MR_MAX_PIXELS = 1 << 24;
 constexpr int MR_MAX_HALF = 32;
 constexpr unsigned long long MR_EMPTY = ~0ull;
-constexpr unsigned MR_MAX_GRID = 1u << 20;       // workgroups of a launch; the kernels stride beyond that
 constexpr unsigned long long MR_ZWORDS = 1ull << 27;       // the global form's z-buffer holds at most this many words (1 GiB)
 
 // the counters of a workgroup: the eight of fgo_map_render_view in its order, then the call's n_nonfinite
@@ -82,7 +83,7 @@ __device__ inline int mr_project(const MrArgs &A, const double (&rt)[12], int64_
   const double p0 = (rt[0] * d0 + rt[3] * d1) + rt[6] * d2, p1 = (rt[1] * d0 + rt[4] * d1) + rt[7] * d2;
   const double z = (rt[2] * d0 + rt[5] * d1) + rt[8] * d2;
   if (!(z > A.z_min && z < A.z_max)) return MR_P_INVALID;
-  f.zq = (int)llrint(z * 1048576.0);             // 0 <= zq < 2^31: z_max <= 2047
+  f.zq = (int)llrint(z * MAP_QUANTA_PER_M);            // 0 <= zq < 2^31: z_max <= 2047
   const double uf = ((A.fx * p0) / z) + A.cx, vf = ((A.fy * p1) / z) + A.cy;
   const double B = 1073741824.0;                 // 2^30
   if (!(uf > -B && uf < B && vf > -B && vf < B)) return MR_P_VALID;          // off-image, NaN included
@@ -115,7 +116,7 @@ __device__ inline void mr_resolve(const MrArgs &A, int64_t view, int64_t pix, un
   if (!(zm > A.z_min && zm < A.z_max)) return;
   c[MR_C_MEAS] += 1;
   if (!covered) return;
-  const long long d = llrint(zm * 1048576.0) - (long long)zq;
+  const long long d = llrint(zm * MAP_QUANTA_PER_M) - (long long)zq;
   c[MR_C_BOTH] += 1;
   c[MR_C_AGREE] += d <= A.tq && d >= -A.tq;
   c[MR_C_CLOSER] += d < -A.tq;
@@ -244,10 +245,6 @@ unsigned long long zbuf_words() {
   return v > 0 ? (unsigned long long)v : MR_ZWORDS;
 }
 
-unsigned grid_for(int64_t tiles) { return (unsigned)(tiles < 1 ? 1 : tiles > (int64_t)MR_MAX_GRID ? MR_MAX_GRID : tiles); }
-
-bool finite_pos(double v) { return v > 0 && v < HUGE_VAL; }
-bool is_finite(double v) { return fabs(v) < HUGE_VAL; }
 bool length_ok(double v) { return v >= 0 && v <= 2047.0; }          // false for NaN
 
 double g_mr_kernel_ms = 0.0;
@@ -283,28 +280,23 @@ extern "C" int fgo_map_render_batch(int device, int64_t n_points, const double *
   const int64_t NP = (int64_t)width * height;
   if (n_views > INT64_MAX / NP || n_views * NP >= (1ll << 31)) return FGO_EINVAL;
   if (channels != 0 && channels != 1 && channels != 3) return FGO_EINVAL;
-  if (!finite_pos(P.fx) || !finite_pos(P.fy) || !finite_pos(P.z_scale) || !is_finite(P.cx) || !is_finite(P.cy)) return FGO_EINVAL;
+  if (!pinhole_ok(P.fx, P.fy, P.cx, P.cy, P.z_scale)) return FGO_EINVAL;
   if (!(P.z_min >= 0) || !(P.z_max <= 2047.0) || !(P.z_min < P.z_max)) return FGO_EINVAL;
   if (P.splat < 0 || P.splat > MR_MAX_HALF || P.max_half < P.splat || P.max_half > MR_MAX_HALF) return FGO_EINVAL;
   if (!length_ok(P.radius) || !length_ok(P.agree_tol)) return FGO_EINVAL;
   if (color_out && channels == 0) return FGO_EINVAL;
   if (n_views > 0 && !pose_w7) return FGO_EINVAL;
   if (n_points > 0 && (!xyz || (color == nullptr) != (channels == 0))) return FGO_EINVAL;
-  if (extrinsic7 && !quat_ok(extrinsic7 + 3)) return FGO_EINVAL;
-  if (view_offset7 && !quat_ok(view_offset7 + 3)) return FGO_EINVAL;
-  for (int64_t v = 0; v < n_views; ++v)
-    if (!quat_ok(pose_w7 + 7 * v + 3)) return FGO_EINVAL;
+  std::vector<double> rt;
+  if ((view_offset7 && !quat_ok(view_offset7 + 3)) || !poses_rt(pose_w7, n_views, extrinsic7, rt)) return FGO_EINVAL;
   std::memset(result, 0, sizeof *result);
   if (n_views == 0) return FGO_OK;
   if (int rc = select_device(device)) return rc;
 
   const size_t nv = (size_t)n_views, np = (size_t)NP, n = (size_t)n_points;
-  std::vector<double> rt(12 * nv);
-  for (size_t v = 0; v < nv; ++v) {
-    if (!view_offset7) { pose_rt(pose_w7 + 7 * v, extrinsic7, rt.data() + 12 * v); continue; }
-    double rt1[12];
-    pose_rt(pose_w7 + 7 * v, extrinsic7, rt1);
-    rt_compose(rt1, view_offset7, rt.data() + 12 * v);
+  if (view_offset7) {                                                          // the view: the sensor with the offset composed on the right
+    const std::vector<double> rt1 = rt;
+    for (size_t v = 0; v < nv; ++v) rt_compose(rt1.data() + 12 * v, view_offset7, rt.data() + 12 * v);
   }
   int form = render_form();
   if (width > MR_STRIP) form = FGO_MAP_RENDER_GLOBAL;                          // a row does not fit a strip
@@ -331,34 +323,31 @@ extern "C" int fgo_map_render_batch(int device, int64_t n_points, const double *
   A.n_strips = form == FGO_MAP_RENDER_TILES ? (height + A.tile_rows - 1) / A.tile_rows : 0;
   A.xyz = S.ptr<double>(h_xyz); A.color = S.ptr<uint8_t>(h_color); A.rt = S.ptr<double>(h_rt); A.depth = S.ptr<uint16_t>(h_depth);
   A.fx = P.fx; A.fy = P.fy; A.cx = P.cx; A.cy = P.cy; A.z_scale = P.z_scale; A.z_min = P.z_min; A.z_max = P.z_max; A.radius = P.radius;
-  A.splat = P.splat; A.max_half = P.max_half; A.tq = llrint(P.agree_tol * 1048576.0);
+  A.splat = P.splat; A.max_half = P.max_half; A.tq = llrint(P.agree_tol * MAP_QUANTA_PER_M);
   for (int k = 0; k < 3; ++k) A.bg[k] = P.background[k];
   A.zbuf = chunk > 0 ? S.ptr<unsigned long long>(h_zbuf) : nullptr;
   A.counts = d_cnt; A.nonfinite = d_cnt + MR_VIEW_COUNTS * nv;
   A.zq_out = S.ptr<int32_t>(h_zq); A.index_out = S.ptr<int32_t>(h_index); A.color_out = S.ptr<uint8_t>(h_cout);
 
-  Events ev;
-  if (hipEventCreate(&ev.a) != hipSuccess || hipEventCreate(&ev.b) != hipSuccess) return FGO_ENUM;
-  (void)hipEventRecord(ev.a, 0);
+  KernelTimer timer;
+  if (!timer.start()) return FGO_ENUM;
   if (form == FGO_MAP_RENDER_TILES) {
-    hipLaunchKernelGGL(k_render_tiles, dim3(grid_for(n_views * A.n_strips)), dim3(MR_T), 0, 0, A);
+    hipLaunchKernelGGL(k_render_tiles, dim3(grid_for(n_views * A.n_strips, 1)), dim3(MR_T), 0, 0, A);
   } else {
     for (int64_t v0 = 0; v0 < n_views; v0 += chunk) {                          // the views in chunks: they share no pixel
       A.view0 = v0; A.n_views = n_views - v0 < chunk ? n_views - v0 : chunk;
       const unsigned long long words = (unsigned long long)A.n_views * np;
-      hipLaunchKernelGGL(k_render_init, dim3(grid_for((int64_t)((words + 256 * 8 - 1) / (256 * 8)))), dim3(256), 0, 0, A.zbuf, words);
+      hipLaunchKernelGGL(k_render_init, dim3(grid_for(words, 256 * 8)), dim3(256), 0, 0, A.zbuf, words);
       if (n_points > 0)
-        hipLaunchKernelGGL(k_render_points, dim3(grid_for(A.n_views * ((n_points + MR_T - 1) / MR_T))), dim3(MR_T), 0, 0, A);
-      hipLaunchKernelGGL(k_render_resolve, dim3(grid_for(A.n_views * ((NP + MR_T - 1) / MR_T))), dim3(MR_T), 0, 0, A);
+        hipLaunchKernelGGL(k_render_points, dim3(grid_for(A.n_views * ((n_points + MR_T - 1) / MR_T), 1)), dim3(MR_T), 0, 0, A);
+      hipLaunchKernelGGL(k_render_resolve, dim3(grid_for(A.n_views * ((NP + MR_T - 1) / MR_T), 1)), dim3(MR_T), 0, 0, A);
     }
   }
-  (void)hipEventRecord(ev.b, 0);
+  timer.stop();
   std::vector<unsigned long long> cnt(n_count);
   if (hipMemcpy(cnt.data(), d_cnt, n_count * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess || hipGetLastError() != hipSuccess)
     return FGO_ENUM;
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, ev.a, ev.b) != hipSuccess) ms = 0;
-  g_mr_kernel_ms = (double)ms;
+  g_mr_kernel_ms = timer.ms();
   if (int rc = S.download()) return rc;
   if (view_out)
     for (size_t v = 0; v < nv; ++v) {

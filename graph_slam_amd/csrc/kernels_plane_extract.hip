@@ -384,13 +384,11 @@ extern "C" int fgo_plane_extract_batch(int device, int64_t n_frames, int width, 
   A.plane = S.ptr<fgo_plane_extract_plane>(h_slot[3]);
   A.label = S.ptr<int8_t>(h_label);
   A.hyp = S.ptr<int32_t>(h_hyp);
-  Events ev;
-  if (hipEventCreate(&ev.a) != hipSuccess || hipEventCreate(&ev.b) != hipSuccess) return FGO_ENUM;
-  (void)hipEventRecord(ev.a, 0);
+  KernelTimer timer;
+  if (!timer.start()) return FGO_ENUM;
   hipLaunchKernelGGL(k_plane_extract, dim3((unsigned)n_frames), dim3(PX_T), 0, 0, A);
-  (void)hipEventRecord(ev.b, 0);
+  timer.stop();
   if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return FGO_ENUM;
-  float ms = 0;
-  g_kernel_ms = hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess ? (double)ms : 0.0;
+  g_kernel_ms = timer.ms();
   return S.download();
 }

@@ -367,14 +367,12 @@ extern "C" int fgo_plane_propagate_batch(int device, int64_t n_frames, int width
   if (lds && hipFuncSetAttribute(reinterpret_cast<const void *>(&k_plane_propagate<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)lds_bytes) != hipSuccess)
     return FGO_ENUM;
-  Events ev;
-  if (hipEventCreate(&ev.a) != hipSuccess || hipEventCreate(&ev.b) != hipSuccess) return FGO_ENUM;
-  (void)hipEventRecord(ev.a, 0);
+  KernelTimer timer;
+  if (!timer.start()) return FGO_ENUM;
   if (lds) hipLaunchKernelGGL(k_plane_propagate<true>, dim3((unsigned)n_pairs), dim3(PX_T), lds_bytes, 0, A);
   else hipLaunchKernelGGL(k_plane_propagate<false>, dim3((unsigned)n_pairs), dim3(PX_T), 0, 0, A);
-  (void)hipEventRecord(ev.b, 0);
+  timer.stop();
   if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return FGO_ENUM;
-  float ms = 0;
-  g_pp_kernel_ms = hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess ? (double)ms : 0.0;
+  g_pp_kernel_ms = timer.ms();
   return S.download();
 }

@@ -491,14 +491,12 @@ extern "C" int fgo_vro_ransac_batch(int device, int64_t n_pairs, const int64_t *
   A.mask = S.ptr<uint8_t>(h_mask);
   A.hyp = S.ptr<int32_t>(h_hyp);
   A.res = S.ptr<fgo_vro_result>(h_res);
-  Events ev;
-  if (hipEventCreate(&ev.a) != hipSuccess || hipEventCreate(&ev.b) != hipSuccess) return FGO_ENUM;
-  (void)hipEventRecord(ev.a, 0);
+  KernelTimer timer;
+  if (!timer.start()) return FGO_ENUM;
   if (g_waves == 1) hipLaunchKernelGGL(k_vro_ransac<1>, dim3((unsigned)n_pairs), dim3(64), 0, 0, A);
   else hipLaunchKernelGGL(k_vro_ransac<4>, dim3((unsigned)n_pairs), dim3(256), 0, 0, A);
-  (void)hipEventRecord(ev.b, 0);
+  timer.stop();
   if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return FGO_ENUM;
-  float ms = 0;
-  g_kernel_ms = hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess ? (double)ms : 0.0;
+  g_kernel_ms = timer.ms();
   return S.download();
 }

@@ -1,7 +1,7 @@
 // Host-side pose arithmetic shared by the map calls that turn a pose7 (t, q_xyzw) into the 12 numbers rt = R row-major, then t, which
 // their kernels use (map fusion, map rendering).  include/fgo.h states the expressions; every product, quotient and sum is rounded on
 // its own (contraction is off in every function here), so that the numpy restatements of the tests reproduce rt bit for bit.
-// quat_ok, the validator that goes with them, is in batch_call.hpp.
+// quat_ok, the validator that goes with them, is in batch_call.hpp, which includes this file, as is poses_rt: rt of all poses of a call.
 #pragma once
 #include <cmath>
 #include <cstring>

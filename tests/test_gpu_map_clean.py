@@ -3,7 +3,7 @@ every result field compared for EQUALITY -- everything that decides an outcome i
 order, so there is nothing to tolerate.  The clouds are built from quanta, so that a distance of exactly T is exactly T: the closed
 radius, the 26 directions across a cell border on both sides of the origin, a chain of 20 000 points (the deepest union-find the
 link kernel can be handed), 10 000 points in one cell (every lane hooks under the same root), a bridge, the size bounds, two fused
-maps with many clusters, points out of range, the floor stage at its ties and edges, the cell lookup at its edge, permutations of
+maps with many clusters, points out of range, the smallest clouds of the cell index, the floor stage at its ties and edges, the cell lookup at its edge, permutations of
 the input, and end to end from depth frames."""
 import numpy as np
 import pytest
@@ -93,6 +93,17 @@ def test_points_out_of_range_take_no_part():
     assert w["n_out_of_range"] == 7 and np.all(w["label"][w["reason"] == 1] == -1) and w["n_clusters"] == 6
     w = _check(x[w["reason"] == 1], P)                                    # nothing but such points
     assert w["n_cells"] == 0 and w["n_clusters"] == 0 and w["n_kept"] == 0 and w["floor_bin"] == -1
+
+
+def test_the_smallest_clouds_the_cell_index_can_go_wrong_on():
+    P = dict(min_cluster_size=1)
+    # nothing but the empty key for the sort, no run head for the gather
+    w = _check(np.array([[np.nan, 0, 0], [1e30, 0, 0], [0, np.inf, 0], [0, 0, -1e30], [40000.0, 0, 0]]), P)
+    assert w["n_cells"] == 0 and w["n_out_of_range"] == 5 and np.all(w["reason"] == 1)
+    w = _check(np.array([[0.1, 0.2, 0.3]]), P)                              # the only run head is at s == 0
+    assert w["n_cells"] == 1 and w["n_clusters"] == 1
+    w = _check(np.full((257, 3), 0.5), P)                                   # one cell, one run, one point past a workgroup
+    assert w["n_cells"] == 1 and w["n_clusters"] == 1 and w["cluster_size"][0] == 257
 
 
 def test_floor_ties_go_to_the_lower_bin_and_the_clearance_is_strict():

@@ -174,6 +174,17 @@ def test_points_out_of_range_take_no_part():
     assert got["n_cells"] == 0 and got["n_out_of_range"] == n_bad and got["n_valid"] == 0
 
 
+def test_the_smallest_clouds_the_cell_index_can_go_wrong_on():
+    P = dict(k=3)
+    # nothing but the empty key for the sort, no run head for the gather
+    got, _ = _check(np.array([[np.nan, 0, 0], [1e30, 0, 0], [0, np.inf, 0], [0, 0, -1e30], [40000.0, 0, 0]]), P)
+    assert np.all(got["status"] == 1) and got["n_out_of_range"] == 5 and got["n_cells"] == 0
+    got, _ = _check(np.array([[0.1, 0.2, 0.3]]), P)                        # the only run head is at s == 0
+    assert got["n_few"] == 1 and got["n_cells"] == 1
+    got, _ = _check(np.full((257, 3), 0.5), P)                             # one cell, one run, one point past a workgroup
+    assert got["n_degenerate"] == 257 and got["n_cells"] == 1
+
+
 def test_every_output_is_bit_identical_for_every_cell():
     x = ref.corner()
     want = _corner_want(20)
