@@ -10,7 +10,6 @@ fixed = np.zeros(n, np.uint8); fixed[0] = 1
 gr = G.Graph(); gr.add_poses(g["poses"], fixed); gr.add_edges(g["ei"], g["ej"], g["meas"], g["info"])
 gr.bench_phase(1, 2)
 out = np.zeros(256)
-G.lib.fgo_debug_read_scratch.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int64]
 assert G.lib.fgo_debug_read_scratch(gr._h, out.ctypes.data_as(C.POINTER(C.c_double)), 256) == 0
 st = out.view(np.int64)
 M = 16      # columns of the stamped panel
