@@ -164,6 +164,10 @@ struct RideItem { int t, task; long long o0; int n, first; };   // first: 1 = st
 // sorts the items inside the XCD-contiguous ranges those workgroups take.  (Here and not in device_plan.hpp: symbolic.cpp is also built
 // without the HIP headers.)
 constexpr int RIDE_PER_WG = 4;
+// Flag in an entry >= 0 of Symbolic::acc_start: the target is a hub whose ridden part sits in scratch blocks, so its own accumulate launch
+// starts from H like a target without riders (symbolic_riders.cpp step 3, structure_upload.cpp); acc_start_op() is the op index without it.
+constexpr int64_t ACC_START_HUB = (int64_t)1 << 62;
+inline int64_t acc_start_op(int64_t start) { return start & ~ACC_START_HUB; }
 
 // undirected block graph of the free poses (CSR, no self loops, no duplicates)
 struct BlockGraph {

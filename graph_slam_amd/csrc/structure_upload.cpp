@@ -148,8 +148,8 @@ int upload_symbolic(fgo_ctx *c, const Ordering &O, const HostTables &T) {
       for (int q = q0; q < q1; ++q) {
         const int t = S.acc_targets[(size_t)q];
         const int64_t rsv = S.acc_start.empty() ? -1 : S.acc_start[(size_t)q];
-        const bool from_h = rsv >= 0 && ((rsv >> 62) & 1);
-        const int64_t rs = rsv >= 0 ? (rsv & ~((int64_t)1 << 62)) : -1;
+        const bool from_h = rsv >= 0 && (rsv & ACC_START_HUB) != 0;
+        const int64_t rs = rsv >= 0 ? acc_start_op(rsv) : -1;
         const bool topb = O.dist && t >= O.top_blk0;
         ad[(size_t)q] = AccDesc{t, (topb || (rs >= 0 && !from_h)) ? -2 : (T.asrc[(size_t)t] >= 0 ? T.asrc[(size_t)t] : -1),
                                 (long long)(rs >= 0 ? rs : (topb ? T.top_ext0[(size_t)(t - O.top_blk0)] : S.op_ptr[(size_t)t])), (long long)S.op_mid[(size_t)t]};

@@ -31,6 +31,7 @@ import pytest
 
 from tests.test_gpu_launch_forms import KAPPA, EPS, ROOT, FACTOR_FORMS, _run_child, _stops, _Ref, _arrays, _forms
 from tests.tri1_two_waves_child import COMPLETE, SYNTH
+from tests.util import build_symstats
 
 gpu = pytest.mark.gpu
 
@@ -48,11 +49,7 @@ RUNS = ["first", "second"]
 
 def test_the_graphs_hold_every_panel_width():
     """CPU: the structure phase of the two synthetic graphs (tools/symstats, task work 1) has the panel widths the docstring states"""
-    exe = os.path.join(ROOT, "tools", "symstats")
-    src = [os.path.join(ROOT, "tools", "symstats.cpp")] + [os.path.join(ROOT, "graph_slam_amd", "csrc", f)
-                                                          for f in ("symbolic.cpp", "ordering.cpp", "synth.cpp")]
-    if not os.path.exists(exe) or any(os.path.getmtime(f) > os.path.getmtime(exe) for f in src):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", "-I" + ROOT, "-o", exe] + src, check=True, cwd=os.path.join(ROOT, "tools"))
+    exe = build_symstats()
     total = [0] * 16
     for g, (n, lookback, loops, seed) in SYNTH.items():
         out = subprocess.run([exe, str(n), str(lookback), str(loops), "64", "1", "1000000000"], capture_output=True, text=True,

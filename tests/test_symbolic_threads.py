@@ -7,17 +7,12 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tools", "symstats")
+from tests.util import build_symstats
 
 
 @pytest.fixture(scope="module")
 def symstats():
-    src = [os.path.join(ROOT, "tools", "symstats.cpp")] + [os.path.join(ROOT, "graph_slam_amd", "csrc", f)
-                                                          for f in ("symbolic.cpp", "ordering.cpp", "synth.cpp")]
-    if not os.path.exists(EXE) or any(os.path.getmtime(f) > os.path.getmtime(EXE) for f in src):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", "-I" + ROOT, "-o", EXE] + src, check=True, cwd=os.path.join(ROOT, "tools"))
-    return EXE
+    return build_symstats()
 
 
 def run(exe, n, threads, leaf=64):

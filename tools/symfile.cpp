@@ -5,6 +5,7 @@
 #include <vector>
 #include <algorithm>
 #include "../graph_slam_amd/csrc/fgo_internal.hpp"
+#include "symbolic_phases.hpp"     // the phase files of build_symbolic: not on the build line
 using namespace fgo;
 static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 int main(int argc, char **argv) {

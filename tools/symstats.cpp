@@ -7,8 +7,51 @@
 #include <algorithm>
 #include "../include/fgo.h"
 #include "../graph_slam_amd/csrc/fgo_internal.hpp"
+#include "symbolic_phases.hpp"     // the phase files of build_symbolic: not on the build line
 using namespace fgo;
 static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// FGO_DIGEST=1: one line per member of struct Symbolic (tests/test_symbolic_digest_cpu.py reads the member names from fgo_internal.hpp and
+// fails if one is missing here) -- vectors as `digest <name> <elements> <fnv64 of the bytes>`, scalars as `digest <name> <value>`
+struct Fnv64 {
+  uint64_t h = 1469598103934665603ull;
+  void mix(const void *p, size_t bytes) { const unsigned char *c = (const unsigned char *)p; for (size_t i = 0; i < bytes; ++i) { h ^= c[i]; h *= 1099511628211ull; } }
+};
+template <class V> static void digest_vec(const char *name, const V &v) {
+  Fnv64 f;
+  f.mix(v.data(), v.size() * sizeof(v[0]));
+  printf("digest %s %zu %016llx\n", name, v.size(), (unsigned long long)f.h);
+}
+static void print_digests(const Symbolic &S) {
+#define DV(m) digest_vec(#m, S.m)
+#define DS(m) printf("digest %s %lld\n", #m, (long long)S.m)
+  DS(nb); DV(perm); DV(iperm); DV(parent); DV(colptr); DV(rowidx); DV(blkcol);
+  DV(op_ptr); DV(op_a); DV(op_b); DV(op_mid); DV(acc_ptr); DV(acc_targets); DV(acc_mid);
+  DV(g2_lvl); DV(g2_tgt); DV(g2_ptr); DV(g2_b); DV(g2_a);
+  DV(rowptr); DV(row_blk); DV(row_col);
+  DV(task_ptr); DV(task_cols); DV(level_ptr);
+  DV(task_panel); DS(n_panels); DV(panel_task); DV(ptri_blk); DV(prow_ptr); DV(prow_idx); DV(prow_blk);
+  DV(level_panel); DV(level_leaf); DV(level_leaf_maxblk); DV(level_leaf_maxops);
+  DV(pchunk_ptr); DV(pchunk_panel); DV(pchunk_row0); DV(pchunk_nrows); DV(panel_chunk0);
+  DV(rchunk_ptr); DV(rchunk_panel); DV(rchunk_s0);
+  DV(row_mid); DV(fchunk_ptr); DV(fchunk_col); DV(fchunk_e0); DV(pcol_fchunk0); DV(pcol_fchunkn);
+  {   // field by field: the struct has padding
+    Fnv64 f;
+    for (const RideItem &it : S.ride_items) { f.mix(&it.t, sizeof it.t); f.mix(&it.task, sizeof it.task); f.mix(&it.o0, sizeof it.o0); f.mix(&it.n, sizeof it.n); f.mix(&it.first, sizeof it.first); }
+    printf("digest ride_items %zu %016llx\n", S.ride_items.size(), (unsigned long long)f.h);
+  }
+  DV(ride_ptr); DS(n_scratch); DV(acc_start);
+  DS(world); DV(dom_col0); DV(seg_group);
+  DS(nnzL); DS(nops); DS(etree_height); DS(max_col_blocks);
+#undef DV
+#undef DS
+  // what the digests cannot show: how many levels take the leaf kernel, how many (non-empty ones) neither it nor the panel kernels
+  int leaf = 0, generic = 0;
+  for (size_t l = 0; l < S.level_panel.size() && l < S.level_leaf.size(); ++l) {
+    leaf += S.level_leaf[l] != 0;
+    generic += !S.level_panel[l] && !S.level_leaf[l] && S.level_ptr[l + 1] > S.level_ptr[l];
+  }
+  printf("count leaf_levels %d\ncount generic_levels %d\n", leaf, generic);
+}
 int main(int argc, char **argv) {
   int64_t N = argc > 1 ? atoll(argv[1]) : 10000;
   int lookback = argc > 2 ? atoi(argv[2]) : 5, nloop = argc > 3 ? atoi(argv[3]) : 4;
@@ -63,7 +106,13 @@ int main(int argc, char **argv) {
   }
   const int world = std::getenv("FGO_WORLD") ? atoi(std::getenv("FGO_WORLD")) : 1;
   if (world > 1) { opt.bal_w = 8.0; nested_dissection(g, opt, perm); }       // (the product's distributed-mode balance weight)
-  Symbolic S; t0 = now(); build_symbolic(g, perm, limit, argc > 6 ? atoll(argv[6]) : limit, S, world); printf("symbolic %.2fs\n", now() - t0);
+  const bool analyse_only = std::getenv("FGO_ANALYSE_ONLY") != nullptr;
+  Symbolic S; t0 = now(); build_symbolic(g, perm, limit, argc > 6 ? atoll(argv[6]) : limit, S, world, analyse_only); printf("symbolic %.2fs\n", now() - t0);
+  if (std::getenv("FGO_DIGEST")) { print_digests(S); return 0; }
+  if (analyse_only) {                                    // (the sections below read tables that were not built)
+    printf("nnzL blocks %lld nops %lld etree_height %d max_col_blocks %d tasks %zu levels %zu\n", (long long)S.nnzL, (long long)S.nops, S.etree_height, S.max_col_blocks, S.task_ptr.size() - 1, S.level_ptr.size() - 1);
+    return 0;
+  }
   if (world > 1) {
     // the replicated top of the distributed mode, segment by segment: what an owner-computes split could divide
     printf("distributed, world %d: top columns %d of %d\n", world, n - S.dom_col0[world], n);
@@ -282,6 +331,7 @@ int main(int argc, char **argv) {
     for (int64_t t = 0; t < S.nnzL; ++t) {
       const int lt = col_level[S.blkcol[t]];
       for (int64_t o = S.op_ptr[t]; o < S.op_ptr[t + 1]; ++o) {
+        if (S.op_a[o] >= S.nnzL) continue;      // a hub target's piece: (scratch block) x (identity block), no column of L behind either
         const int ls = col_level[S.blkcol[S.op_a[o]]];
         if (o < S.op_mid[t]) { if (ls == 0) ++ext0; else ++extp; } else { if (lt == 0) ++int0; else ++intp; }
       }
