@@ -301,6 +301,9 @@ int ba_upload(fgo_ctx *c, const VarIndex &V, const Ordering &O, const BaTables &
     HIPCHK(c, ba.d_op_a.upload(BA.op_a, s)); HIPCHK(c, ba.d_op_b.upload(BA.op_b, s)); HIPCHK(c, ba.d_op_lm.upload(BA.op_lm, s));
     for (int i = 0; i < 2; ++i) {
       HIPCHK(c, ba.d_W[i].alloc(n_obs * 18)); HIPCHK(c, ba.d_Hpp[i].alloc((size_t)n_lm * 6)); HIPCHK(c, ba.d_bp[i].alloc((size_t)n_lm * 3));
+      // the observations of fixed cameras (the first o_first) have no coupling block and k_ba_cameras never writes one, but the
+      // padding entries of k_ba_schur read block 0 and multiply it by zero: whatever the allocation held must not be a NaN
+      if (BA.o_first > 0) HIPCHK(c, hipMemsetAsync(ba.d_W[i].p, 0, sizeof(double) * 18 * (size_t)BA.o_first, s));
     }
     HIPCHK(c, ba.d_Hinv.alloc((size_t)n_lm * 6)); HIPCHK(c, ba.d_zp.alloc((size_t)n_lm * 3)); HIPCHK(c, ba.d_pt_val.alloc((size_t)n_lm * 3));
     HIPCHK(c, ba.d_Hred.alloc((size_t)c->plan.n_hblocks * 36)); HIPCHK(c, ba.d_bred.alloc((size_t)O.nb * 6));
