@@ -19,6 +19,7 @@
 #include "../../include/fgo.h"
 #include "device_plan.hpp"
 #include "fgo_internal.hpp"
+#include "isam_dirty.hpp"
 #include "rccl_min.hpp"
 
 namespace fgo {
@@ -58,6 +59,60 @@ struct DevBuf {
 //   isam_step       the factor of the previous ISAM2 step, d_y its forward solution: the next update may re-factor only the
 //                   tasks on the paths from the affected variables to the roots
 enum class LHolds { scratch, undamped, undamped_sigma, isam_step };
+
+// Everything fgo_isam2_* owns (fgo_ctx::isam), grouped by lifetime.  DESIGN.md "Three sweep modes" says what each carried-over
+// item is and what invalidates it.
+struct IsamState {
+  // ---- state, from the first update to fgo_isam2_reset: linearisation point and linear solution per variable, variable order
+  DevBuf<double> d_theta, d_delta;  // 8 / 6 doubles per variable
+  int64_t n = 0;                    // variables the state covers (variables added later start at their initial value, delta 0)
+  int64_t E_seen = 0, NI_seen = 0, NP_seen = 0;   // factors the previous update already knew
+  // ---- per structure (partial_sweep_tables() in structure_upload.cpp; col_task empty: a structure without them).  An update
+  // re-runs only the tasks on the paths from the affected variables to the roots, launched as index ranges instead of full
+  // grids (device_plan.hpp PartialSweep): per task [first, end) of its items in the level-wise lists, the level of every task;
+  // tk_ok: every list was found in task order when the tables were built
+  std::vector<int> col_task;        // [nb] task of every column (host)
+  std::vector<int64_t> tk_s0, tk_s1, tk_l0, tk_l1;
+  std::vector<int> tk_g0, tk_g1, tk_c0, tk_c1, task_level, lvl_lo, lvl_hi;
+  bool tk_ok = false;
+  DevBuf<int> d_acc_task, d_g2_task, d_tcol_task;
+  DevBuf<double> d_y;               // forward solution of the previous update (L_holds == isam_step)
+  DevBuf<unsigned char> d_moved, d_task_dirty, d_col_dirty, d_moved_next, d_lin_mask;
+  DevBuf<double> d_chi_var;         // per-variable chi2 of the masked re-linearisation (kernels_gtsam.hip)
+  PartialSweep partial_sweep(const Symbolic &S) const {   // the ranged sweep of lvl_lo / lvl_hi over the per-task tables
+    return PartialSweep{lvl_lo.data(), lvl_hi.data(), tk_s0.data(), tk_s1.data(), tk_l0.data(), tk_l1.data(),
+                        tk_g0.data(), tk_g1.data(), tk_c0.data(), tk_c1.data(), S.task_ptr.data()};
+  }
+  // ---- pinned host flags (isam_dirty.hpp), sized for the structure
+  unsigned char *h_flags = nullptr;
+  size_t h_flags_cap = 0;
+  IsamFlags flags;
+  // ---- carried over from the previous update; a successful update sets them, invalidate_carry() is the only place that clears
+  // them (the resident factor is the fourth such item: L_holds == isam_step, dropped by drop_isam_step)
+  enum : unsigned {
+    CARRY_H = 1,                    // H / b of the side buffers and d_chi_var are in place: only the affected variables are gathered again
+    CARRY_LOOK = 2,                 // flags.moved_next says which variables a relinearisation at look_thr moves, laid out for look_nx slots
+    CARRY_SOLUTION = 4              // wild.d_xprev holds the solution of the previous update on this structure
+  };
+  unsigned carry = 0;
+  double look_thr = -1;
+  int64_t look_nx = 0;
+  void invalidate_carry(unsigned what = ~0u) { carry &= ~what; }
+  // ---- what the last update on this structure ran (fgo_debug_isam_last / fgo_debug_launch_census walk and read this sweep)
+  enum class Sweep { full = 0, masked = 1, ranged = 2 };   // masked: task_dirty over full grids; ranged: lvl_lo / lvl_hi hold its ranges
+  struct Last {
+    Sweep sweep = Sweep::full;
+    bool cut = false;               // its back-substitution was cut (wild.d_bwd_run / d_chg)
+    IsamSets set;                   // the entries of flags it set; set.tasks are its dirty tasks
+    void clear() { sweep = Sweep::full; cut = false; set.clear(); }
+  } last;
+  // ---- wildfire back-substitution (fgo_isam2_set_wildfire): previous solution in column order, per-task / per-column flags
+  struct Wild {
+    double thr = 0;
+    DevBuf<double> d_xprev;
+    DevBuf<unsigned char> d_bwd_run, d_chg;
+  } wild;
+};
 
 }  // namespace fgo
 
@@ -170,48 +225,7 @@ struct fgo_ctx {
     int64_t n_off = 0, n_groups = 0;   // candidates whose Sigma_ab was off the factor's pattern; block columns solved for them
     double ms_kernel = 0, ms_solves = 0;
   } gate;
-  // ---- ISAM2 state (fgo_isam2_update): linearisation point and linear solution per variable, variable order
-  fgo::DevBuf<double> d_theta, d_delta;  // 8 / 6 doubles per variable
-  // partial re-factorisation (L_holds == isam_step): an update re-runs only the tasks on the paths from the affected variables
-  // to the roots (task_dirty)
-  int64_t isam_E_seen = 0, isam_NI_seen = 0, isam_NP_seen = 0;   // factors the previous step already knew
-  std::vector<int> col_task;        // [nb] task of every column (host)
-  fgo::DevBuf<double> d_y;
-  fgo::DevBuf<unsigned char> d_moved, d_task_dirty, d_col_dirty, d_moved_next;
-  unsigned char *h_flags = nullptr;  // pinned staging: [NX] moved | [ntask] task_dirty | [nb] col_dirty | [NX] moved_next | [NX] affected
-  // fgo_isam2_update decides at its END which variables the next call will relinearise (delta and the threshold are known
-  // then) and brings the flags to the host with its final synchronisation: the next call starts without a mid-stream one
-  // masked re-linearisation (kernels_gtsam.hip): H / b of the side buffers and the per-variable chi2 of the previous update
-  // are still in place, so only the variables whose factors changed are gathered again
-  fgo::DevBuf<unsigned char> d_lin_mask;
-  fgo::DevBuf<double> d_chi_var;
-  bool isam_H_valid = false;
-  std::vector<int> isam_set_tasks, isam_set_cols;      // entries of the pinned flag arrays set by the previous update (cleared sparsely)
-  std::vector<int64_t> isam_set_aff;
-  // partial sweeps launch index ranges instead of full grids (device_plan.hpp PartialSweep): per task [first, end) of its items in
-  // the level-wise lists, the level of every task; tk_ok: every list was found in task order when the tables were built
-  std::vector<int64_t> tk_s0, tk_s1, tk_l0, tk_l1;
-  std::vector<int> tk_g0, tk_g1, tk_c0, tk_c1, task_level, lvl_lo, lvl_hi;
-  bool tk_ok = false;
-  // what the last fgo_isam2_update on this structure ran (debug readers): 0 full sweep, 1 masked (task_dirty, full grids), 2 ranged
-  // (lvl_lo / lvl_hi hold its ranges, isam_set_tasks its dirty tasks); whether its back-substitution was cut (d_bwd_run / d_chg)
-  int isam_last_sweep = 0;
-  bool isam_last_cut = false;
-  fgo::PartialSweep partial_sweep() const {            // the ranged sweep of lvl_lo / lvl_hi over the per-task tables
-    return fgo::PartialSweep{lvl_lo.data(), lvl_hi.data(), tk_s0.data(), tk_s1.data(), tk_l0.data(), tk_l1.data(),
-                             tk_g0.data(), tk_g1.data(), tk_c0.data(), tk_c1.data(), S.task_ptr.data()};
-  }
-  // wildfire back-substitution (fgo_isam2_set_wildfire): previous solution in column order, per-task / per-column flags
-  double wild_thr = 0;
-  bool wild_valid = false;                           // d_xprev holds the solution of the previous update on THIS structure
-  fgo::DevBuf<double> d_xprev;
-  fgo::DevBuf<unsigned char> d_bwd_run, d_chg;
-  bool isam_moved_valid = false;
-  double isam_moved_thr = -1;
-  int64_t isam_moved_nx = 0;
-  size_t h_flags_cap = 0;
-  fgo::DevBuf<int> d_acc_task, d_g2_task, d_tcol_task;
-  int64_t isam_n = 0;               // variables the state covers (variables added later start at their initial value, delta 0)
+  fgo::IsamState isam;              // everything fgo_isam2_* owns (above)
   // ---- incremental mode (fgo_isam2_update on a growing graph): the structure is built for the graph PLUS a reserve of
   // phantom variables, each coupled to the `window` variables before it (DESIGN.md "Incremental updates").  New variables
   // claim phantom slots and new factors whose variable pairs already exist in the structure are appended in place

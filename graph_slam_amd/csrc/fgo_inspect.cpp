@@ -163,7 +163,7 @@ int fgo_debug_launch_census(fgo_ctx *c, int fused, int64_t *launches, int64_t *w
   if (fused != 2) ba_off(c);                            // the structure fgo_solve_step / fgo_debug_solve_fused run on
   // fused == 2: the factor sweep as the last fgo_isam2_update ran it -- its dirty flags in the walked plan and, where it was ranged,
   // its PartialSweep -- so the launcher's own range arithmetic answers
-  if (fused == 2 && (c->structure_dirty || c->isam_last_sweep == 0 || c->col_task.empty()))
+  if (fused == 2 && (c->structure_dirty || c->isam.last.sweep == IsamState::Sweep::full || c->isam.col_task.empty()))
     return fail(c, FGO_ESTATE, "fgo_debug_launch_census: the last fgo_isam2_update on this structure was not a partial sweep");
   int rc = ensure_ready(c);
   if (rc) return rc;
@@ -173,9 +173,9 @@ int fgo_debug_launch_census(fgo_ctx *c, int fused, int64_t *launches, int64_t *w
   if (!b || !x) return fail(c, FGO_ESTATE, "fgo_debug_launch_census: the right-hand side / solution buffers are not allocated");
   DevPlan plan = c->plan;
   PartialSweep ps{};
-  if (fused == 2) { plan.task_dirty = c->d_task_dirty.p; if (c->isam_last_sweep == 2) ps = c->partial_sweep(); }
+  if (fused == 2) { plan.task_dirty = c->isam.d_task_dirty.p; if (c->isam.last.sweep == IsamState::Sweep::ranged) ps = c->isam.partial_sweep(c->S); }
   launch_factor(plan, c->sched, c->d_H[c->cur].p, c->d_L.p, c->d_scal.p + 3, c->d_fail.p, c->stream, fused ? b : nullptr, fused ? x : nullptr, PHASE_ALL,
-                fused == 2 && c->isam_last_sweep == 2 ? &ps : nullptr, nullptr, &cz);
+                fused == 2 && c->isam.last.sweep == IsamState::Sweep::ranged ? &ps : nullptr, nullptr, &cz);
   launch_solve(c->plan, c->sched, c->d_L.p, b, x, c->stream, fused != 0, PHASE_ALL, nullptr, &cz);
   for (int f = 0; f < std::min<int>(form_cap, LF_COUNT); ++f) {
     if (launches) launches[f] = cz.launches[f];
@@ -217,23 +217,23 @@ int fgo_debug_isam_last(fgo_ctx *c, int *info5, int *level_lo, int *level_hi, in
                         unsigned char *task_run, int task_cap, int *var_task, unsigned char *var_chg, double *var_delta, int64_t var_cap) try {
   if (!c || level_cap < 0 || task_cap < 0 || var_cap < 0) return FGO_EINVAL;
   (void)hipSetDevice(c->cfg.device);
-  if (c->structure_dirty || c->col_task.empty() || !c->inc.valid || c->isam_n <= 0)
+  if (c->structure_dirty || c->isam.col_task.empty() || !c->inc.valid || c->isam.n <= 0)
     return fail(c, FGO_ESTATE, "fgo_debug_isam_last: no fgo_isam2_update has run on the current structure");
   const int nl = c->sched.n_levels, ntask = (int)c->S.task_ptr.size() - 1, nb = c->plan.nb;
-  const int64_t N = c->isam_n;
-  if (info5) { info5[0] = c->isam_last_sweep; info5[1] = c->isam_last_cut ? 1 : 0; info5[2] = nl; info5[3] = ntask; info5[4] = c->sched.bchain_low; }
-  const bool ranged = c->isam_last_sweep == 2;
+  const int64_t N = c->isam.n;
+  if (info5) { info5[0] = (int)c->isam.last.sweep; info5[1] = c->isam.last.cut ? 1 : 0; info5[2] = nl; info5[3] = ntask; info5[4] = c->sched.bchain_low; }
+  const bool ranged = c->isam.last.sweep == IsamState::Sweep::ranged;
   for (int l = 0; l < std::min(level_cap, nl); ++l) {
-    if (level_lo) level_lo[l] = ranged ? c->lvl_lo[(size_t)l] : c->sched.level_ptr[l];
-    if (level_hi) level_hi[l] = ranged ? c->lvl_hi[(size_t)l] : c->sched.level_ptr[l + 1] - 1;
+    if (level_lo) level_lo[l] = ranged ? c->isam.lvl_lo[(size_t)l] : c->sched.level_ptr[l];
+    if (level_hi) level_hi[l] = ranged ? c->isam.lvl_hi[(size_t)l] : c->sched.level_ptr[l + 1] - 1;
     if (level_ntask) level_ntask[l] = c->sched.level_ptr[l + 1] - c->sched.level_ptr[l];
   }
   if ((level_fwd || level_fwtab) && level_cap > 0) {    // the launcher's own record of the sweep's forward-role workgroups (nothing is launched)
     LaunchCensus cz;
     DevPlan plan = c->plan;
     PartialSweep ps{};
-    if (c->isam_last_sweep != 0) plan.task_dirty = c->d_task_dirty.p;
-    if (ranged) ps = c->partial_sweep();
+    if (c->isam.last.sweep != IsamState::Sweep::full) plan.task_dirty = c->isam.d_task_dirty.p;
+    if (ranged) ps = c->isam.partial_sweep(c->S);
     launch_factor(plan, c->sched, c->d_H[c->cur].p, c->d_L.p, c->d_scal.p + 3, c->d_fail.p, c->stream, c->d_b[c->cur].p, c->d_x.p, PHASE_ALL,
                   ranged ? &ps : nullptr, nullptr, &cz);
     for (int l = 0; l < std::min(level_cap, nl); ++l) {
@@ -242,28 +242,28 @@ int fgo_debug_isam_last(fgo_ctx *c, int *info5, int *level_lo, int *level_hi, in
     }
   }
   const int nt = std::min(task_cap, ntask);
-  if (task_level) for (int t = 0; t < nt; ++t) task_level[t] = c->task_level[(size_t)t];
+  if (task_level) for (int t = 0; t < nt; ++t) task_level[t] = c->isam.task_level[(size_t)t];
   if (task_dirty) {                                     // (a full sweep runs every task)
-    std::fill(task_dirty, task_dirty + nt, (unsigned char)(c->isam_last_sweep == 0 ? 1 : 0));
-    if (c->isam_last_sweep != 0) for (int t : c->isam_set_tasks) if (t < nt) task_dirty[t] = 1;
+    std::fill(task_dirty, task_dirty + nt, (unsigned char)(c->isam.last.sweep == IsamState::Sweep::full ? 1 : 0));
+    if (c->isam.last.sweep != IsamState::Sweep::full) for (int t : c->isam.last.set.tasks) if (t < nt) task_dirty[t] = 1;
   }
   std::vector<unsigned char> chg;
-  if (c->isam_last_cut && (task_run || var_chg)) {
+  if (c->isam.last.cut && (task_run || var_chg)) {
     std::vector<unsigned char> run((size_t)ntask);
     chg.resize((size_t)nb);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(run.data(), c->d_bwd_run.p, (size_t)ntask, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(chg.data(), c->d_chg.p, (size_t)nb, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(run.data(), c->isam.wild.d_bwd_run.p, (size_t)ntask, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(chg.data(), c->isam.wild.d_chg.p, (size_t)nb, hipMemcpyDeviceToHost));
     // (the levels of the backward chain are always solved and have no run flag)
-    if (task_run) for (int t = 0; t < nt; ++t) task_run[t] = c->task_level[(size_t)t] >= c->sched.bchain_low ? 1 : run[(size_t)t];
+    if (task_run) for (int t = 0; t < nt; ++t) task_run[t] = c->isam.task_level[(size_t)t] >= c->sched.bchain_low ? 1 : run[(size_t)t];
   } else if (task_run) std::fill(task_run, task_run + nt, (unsigned char)1);
   const int64_t nv = std::min<int64_t>(var_cap, N);
-  for (int64_t v = 0; v < nv; ++v) {                    // variables in the order they were added (phantom slots: beyond isam_n)
+  for (int64_t v = 0; v < nv; ++v) {                    // variables in the order they were added (phantom slots: beyond isam.n)
     const int k = c->inc.pose_col[(size_t)v];
-    if (var_task) var_task[v] = k >= 0 ? c->col_task[(size_t)k] : -1;
+    if (var_task) var_task[v] = k >= 0 ? c->isam.col_task[(size_t)k] : -1;
     if (var_chg) var_chg[v] = (k >= 0 && !chg.empty()) ? chg[(size_t)k] : 0;
   }
-  if (var_delta && nv > 0) HIPCHK(c, hipMemcpy(var_delta, c->d_delta.p, sizeof(double) * 6 * (size_t)nv, hipMemcpyDeviceToHost));
+  if (var_delta && nv > 0) HIPCHK(c, hipMemcpy(var_delta, c->isam.d_delta.p, sizeof(double) * 6 * (size_t)nv, hipMemcpyDeviceToHost));
   return (int)std::min<int64_t>(N, INT32_MAX);
 } FGO_CATCH_INT(c)
 

@@ -165,27 +165,28 @@ int partial_sweep_tables(fgo_ctx *c, const VarIndex &V, const Ordering &O, const
   hipStream_t s = c->stream;
   const Symbolic &S = c->S;
   const int nb = O.nb;
-  c->col_task.clear();
+  IsamState &I = c->isam;
+  I.col_task.clear();
   if (c->isam_incremental && !O.dist) {               // partial sweeps: task of every column / accumulate target / column group
     const int ntask = (int)S.task_ptr.size() - 1;
-    c->col_task.assign((size_t)nb, 0);
+    I.col_task.assign((size_t)nb, 0);
     std::vector<int> tcol_task((size_t)nb);
     for (int t = 0; t < ntask; ++t)
-      for (int q = S.task_ptr[t]; q < S.task_ptr[t + 1]; ++q) { c->col_task[S.task_cols[q]] = t; tcol_task[(size_t)q] = t; }
+      for (int q = S.task_ptr[t]; q < S.task_ptr[t + 1]; ++q) { I.col_task[S.task_cols[q]] = t; tcol_task[(size_t)q] = t; }
     std::vector<int> acc_task(S.acc_targets.size()), g2_task(S.g2_ptr.size() - 1);
-    for (size_t q = 0; q < acc_task.size(); ++q) acc_task[q] = c->col_task[S.blkcol[S.acc_targets[q]]];
+    for (size_t q = 0; q < acc_task.size(); ++q) acc_task[q] = I.col_task[S.blkcol[S.acc_targets[q]]];
     for (size_t q = 0; q < g2_task.size(); ++q) {
       int t = -1;
-      for (int x = 0; x < ACC2_G && t < 0; ++x) if (S.g2_tgt[q * ACC2_G + x] >= 0) t = c->col_task[S.blkcol[S.g2_tgt[q * ACC2_G + x]]];
+      for (int x = 0; x < ACC2_G && t < 0; ++x) if (S.g2_tgt[q * ACC2_G + x] >= 0) t = I.col_task[S.blkcol[S.g2_tgt[q * ACC2_G + x]]];
       g2_task[q] = t < 0 ? 0 : t;
     }
     // per task: where its items sit in the level-wise lists (partial sweeps launch the covering ranges only)
     {
       const int nl = (int)S.level_ptr.size() - 1;
-      c->tk_s0.assign((size_t)ntask, 0); c->tk_s1 = c->tk_s0; c->tk_l0 = c->tk_s0; c->tk_l1 = c->tk_s0;
-      c->tk_g0.assign((size_t)ntask, 0); c->tk_g1 = c->tk_g0; c->tk_c0 = c->tk_g0; c->tk_c1 = c->tk_g0;
-      c->task_level = task_level;
-      c->lvl_lo.assign((size_t)nl, 0); c->lvl_hi.assign((size_t)nl, -1);
+      I.tk_s0.assign((size_t)ntask, 0); I.tk_s1 = I.tk_s0; I.tk_l0 = I.tk_s0; I.tk_l1 = I.tk_s0;
+      I.tk_g0.assign((size_t)ntask, 0); I.tk_g1 = I.tk_g0; I.tk_c0 = I.tk_g0; I.tk_c1 = I.tk_g0;
+      I.task_level = task_level;
+      I.lvl_lo.assign((size_t)nl, 0); I.lvl_hi.assign((size_t)nl, -1);
       bool ok = true;
       // items [b, e) of a level, task(q) of an item (-1: belongs to whatever task is current) -> per task [first, end)
       auto scan = [&](const char *kind, int l, int64_t b, int64_t e, auto task_at, auto &first, auto &end) {
@@ -200,44 +201,40 @@ int partial_sweep_tables(fgo_ctx *c, const VarIndex &V, const Ordering &O, const
         if (was_ok && !ok && tm.prof) std::fprintf(stderr, "[fgo build]    %s of level %d not in task order: item %lld of [%lld, %lld) has task %d, level tasks [%d, %d)\n", kind, l, (long long)q, (long long)b, (long long)e, task_at(q), S.level_ptr[l], S.level_ptr[l + 1]);
       };
       for (int l = 0; l < nl; ++l) {
-        scan("short targets", l, S.acc_ptr[l], S.acc_mid[l], [&](int64_t q) { return acc_task[(size_t)q]; }, c->tk_s0, c->tk_s1);
-        scan("long targets", l, S.acc_mid[l], S.acc_ptr[l + 1], [&](int64_t q) { return acc_task[(size_t)q]; }, c->tk_l0, c->tk_l1);
+        scan("short targets", l, S.acc_ptr[l], S.acc_mid[l], [&](int64_t q) { return acc_task[(size_t)q]; }, I.tk_s0, I.tk_s1);
+        scan("long targets", l, S.acc_mid[l], S.acc_ptr[l + 1], [&](int64_t q) { return acc_task[(size_t)q]; }, I.tk_l0, I.tk_l1);
         if (!S.g2_lvl.empty())
           scan("column groups", l, S.g2_lvl[l], S.g2_lvl[l + 1], [&](int64_t q) {
-            for (int x = 0; x < ACC2_G; ++x) if (S.g2_tgt[(size_t)q * ACC2_G + x] >= 0) return c->col_task[S.blkcol[S.g2_tgt[(size_t)q * ACC2_G + x]]];
-            return -1; }, c->tk_g0, c->tk_g1);
-        scan("row chunks", l, S.rchunk_ptr[l], S.rchunk_ptr[l + 1], [&](int64_t q) { return S.panel_task[S.rchunk_panel[(size_t)q]]; }, c->tk_c0, c->tk_c1);
+            for (int x = 0; x < ACC2_G; ++x) if (S.g2_tgt[(size_t)q * ACC2_G + x] >= 0) return I.col_task[S.blkcol[S.g2_tgt[(size_t)q * ACC2_G + x]]];
+            return -1; }, I.tk_g0, I.tk_g1);
+        scan("row chunks", l, S.rchunk_ptr[l], S.rchunk_ptr[l + 1], [&](int64_t q) { return S.panel_task[S.rchunk_panel[(size_t)q]]; }, I.tk_c0, I.tk_c1);
       }
-      c->tk_ok = ok && tune("isam_ranges", 1) != 0;
+      I.tk_ok = ok && tune("isam_ranges", 1) != 0;
     }
-    HIPCHK(c, c->d_acc_task.upload(acc_task, s));
-    HIPCHK(c, c->d_g2_task.upload(g2_task, s));
-    HIPCHK(c, c->d_tcol_task.upload(tcol_task, s));
-    HIPCHK(c, c->d_task_dirty.alloc((size_t)ntask));
-    HIPCHK(c, c->d_col_dirty.alloc((size_t)nb));
-    HIPCHK(c, c->d_moved.alloc((size_t)V.NX));
-    HIPCHK(c, c->d_moved_next.alloc((size_t)V.NX));
-    HIPCHK(c, c->d_lin_mask.alloc((size_t)V.NX));
-    HIPCHK(c, c->d_chi_var.alloc((size_t)V.NX));
-    HIPCHK(c, c->d_xprev.alloc((size_t)nb * 6));
-    HIPCHK(c, c->d_bwd_run.alloc((size_t)ntask));
-    HIPCHK(c, c->d_chg.alloc((size_t)nb));
-    c->wild_valid = false;
-    c->isam_last_sweep = 0; c->isam_last_cut = false;
-    c->isam_moved_valid = false;                    // (the flags of the previous update were laid out for the previous structure)
-    c->isam_H_valid = false;
-    HIPCHK(c, c->d_y.alloc((size_t)nb * 6));
-    {
-      const size_t need = 3 * (size_t)V.NX + (size_t)ntask + (size_t)nb;
-      if (need > c->h_flags_cap) {
-        if (c->h_flags) (void)hipHostFree(c->h_flags);
-        c->h_flags = nullptr; c->h_flags_cap = 0;
-        HIPCHK(c, hipHostMalloc((void **)&c->h_flags, need + need / 4, hipHostMallocDefault));
-        c->h_flags_cap = need + need / 4;
-      }
-      std::memset(c->h_flags, 0, need);             // fgo_isam2_update keeps the flag arrays clean between calls (sparse set / clear)
-      c->isam_set_tasks.clear(); c->isam_set_cols.clear(); c->isam_set_aff.clear();
+    HIPCHK(c, I.d_acc_task.upload(acc_task, s));
+    HIPCHK(c, I.d_g2_task.upload(g2_task, s));
+    HIPCHK(c, I.d_tcol_task.upload(tcol_task, s));
+    HIPCHK(c, I.d_task_dirty.alloc((size_t)ntask));
+    HIPCHK(c, I.d_col_dirty.alloc((size_t)nb));
+    HIPCHK(c, I.d_moved.alloc((size_t)V.NX));
+    HIPCHK(c, I.d_moved_next.alloc((size_t)V.NX));
+    HIPCHK(c, I.d_lin_mask.alloc((size_t)V.NX));
+    HIPCHK(c, I.d_chi_var.alloc((size_t)V.NX));
+    HIPCHK(c, I.wild.d_xprev.alloc((size_t)nb * 6));
+    HIPCHK(c, I.wild.d_bwd_run.alloc((size_t)ntask));
+    HIPCHK(c, I.wild.d_chg.alloc((size_t)nb));
+    I.invalidate_carry();                           // (what the previous update left was laid out for the previous structure)
+    I.last.clear();
+    HIPCHK(c, I.d_y.alloc((size_t)nb * 6));
+    const size_t need = isam_flags(nullptr, V.NX, ntask, nb).bytes;
+    if (need > I.h_flags_cap) {
+      if (I.h_flags) (void)hipHostFree(I.h_flags);
+      I.h_flags = nullptr; I.h_flags_cap = 0; I.flags = IsamFlags{};
+      HIPCHK(c, hipHostMalloc((void **)&I.h_flags, need + need / 4, hipHostMallocDefault));
+      I.h_flags_cap = need + need / 4;
     }
+    I.flags = isam_flags(I.h_flags, V.NX, ntask, nb);
+    std::memset(I.h_flags, 0, need);                // fgo_isam2_update keeps the flag arrays clean between calls (sparse set / clear)
     HIPCHK(c, hipStreamSynchronize(s));             // the staging vectors die here
   }
   return FGO_OK;
@@ -461,7 +458,7 @@ void fill_plan(fgo_ctx *c, const VarIndex &V, const Ordering &O, const HostTable
   P.op_ptr = c->d_op_ptr.p; P.op_mid = c->d_op_mid.p; P.op_a = c->d_op_a.p; P.op_b = c->d_op_b.p;
   P.acc_targets = c->d_acc_targets.p;
   P.g2_tgt = c->d_g2_tgt.p; P.g2_ptr = c->d_g2_ptr.p; P.g2_b = c->d_g2_b.p; P.g2_a = c->d_g2_a.p;
-  P.task_dirty = nullptr; P.acc_task = c->d_acc_task.p; P.g2_task = c->d_g2_task.p; P.tcol_task = c->d_tcol_task.p;
+  P.task_dirty = nullptr; P.acc_task = c->isam.d_acc_task.p; P.g2_task = c->isam.d_g2_task.p; P.tcol_task = c->isam.d_tcol_task.p;
   P.ride_xcd = (int)tune("ride_xcd", 1);
   P.ride_items = S.ride_items.empty() ? nullptr : c->d_ride_items.p; P.acc_start = S.acc_start.empty() ? nullptr : c->d_acc_start.p; P.acc_desc = c->d_acc_desc.p;
   P.rowptr = c->d_rowptr.p; P.row_blk = c->d_row_blk.p; P.row_col = c->d_row_col.p;

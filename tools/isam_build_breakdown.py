@@ -1,4 +1,4 @@
-import sys, time; sys.path.insert(0, "/root/repo")
+import os, sys, time; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import graph_slam_amd as G
 sizes = [int(a) for a in sys.argv[1:]] or [2000, 20000]
