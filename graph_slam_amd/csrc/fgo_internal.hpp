@@ -286,7 +286,7 @@ struct OrderingOptions {
   // vertices with degree > max(dense_min, dense_factor * mean degree) are hubs: eliminated last (0 disables)
   double dense_factor = 10.0;
   int dense_min = 64;
-  // time dissection (graphs whose vertex index is time; ordering.cpp split_by_index): smaller side of a cut >= time_side of the
+  // time dissection (graphs whose vertex index is time; ordering_cuts.cpp split_by_index): smaller side of a cut >= time_side of the
   // region, measured in vertices (time_weight = 0) or in 1 + time_weight x crossing edges (loop-dense stretches count for more)
   double time_side = 0.30, time_weight = 0.0;
   // time dissection under RECOVERED labels (round 6: one Cuthill-McKee pass when the vertex index is not time).  Off for graphs of mixed
@@ -295,7 +295,22 @@ struct OrderingOptions {
   bool time_recover = true;
 };
 
-void nested_dissection(const BlockGraph &g, const OrderingOptions &opt, std::vector<int> &perm);
+// Which paths of the dissection a call took (tools/symstats prints them under FGO_DIGEST; tests/test_symbolic_digest_cpu.py holds every
+// pinned case to the path it exists for).  Counted per worker and summed at the end; they do not depend on the thread count.
+enum OrderingPath {
+  ND_INDEX_CUTS, ND_INDEX_CUTS_CLEAN,               // regions cut by index; of those, at a rank that no edge crosses
+  ND_LEVEL_CUTS, ND_LEVEL_CUTS_COVER,               // regions cut by a level structure; of those, the minimum cover shrank the separator
+  ND_NO_CUT, ND_DISCONNECTED,                       // regions ordered as a leaf for want of a cut; regions taken apart into components
+  ND_LEAF_SEARCHED, ND_LEAF_SMALL, ND_LEAF_LARGE,   // leaf orderings: minimum degree / passed through with <= 2 / with > 384 vertices
+  ND_RESTORE_COPY, ND_RESTORE_BFS,                  // the winning level structure restored from the kept copy / by one more BFS
+  ND_HUBS, ND_TIME_MODE,                            // vertices taken out as hubs; 0 level cuts, 1 index = time, 2 recovered labels
+  ND_PATHS
+};
+constexpr const char *ORDERING_PATH_NAMES[ND_PATHS] = {"index_cuts", "index_cuts_clean", "level_cuts", "level_cuts_cover", "no_cut", "disconnected",
+  "leaf_searched", "leaf_small", "leaf_large", "restore_copy", "restore_bfs", "hubs", "time_mode"};
+struct OrderingStats { int64_t n[ND_PATHS] = {}; };
+
+void nested_dissection(const BlockGraph &g, const OrderingOptions &opt, std::vector<int> &perm, OrderingStats *stats = nullptr);
 void build_symbolic(const BlockGraph &g, const std::vector<int> &perm, int64_t task_work_limit, int64_t chain_work_limit, Symbolic &S, int world = 1,
                     bool analyse_only = false);   // analyse_only: stop once fill, block updates and levels are known (a fifth of the time)
 

@@ -60,7 +60,7 @@ static int classify(fgo_ctx *c, VarIndex &V, BuildTimer &tm) {
   return FGO_OK;
 }
 
-// ---- nested dissection, symbolic factorisation, schedule (ordering.cpp, symbolic.cpp)
+// ---- nested dissection, symbolic factorisation, schedule (ordering*.cpp, symbolic*.cpp)
 static int order_and_symbolic(fgo_ctx *c, const VarIndex &V, const PairGraph &G, Ordering &O, BuildTimer &tm) {
   Symbolic &S = c->S;
   const char *wl = std::getenv("FGO_TASK_WORK");

@@ -143,7 +143,7 @@ def test_manhattan_10k_with_loop_closures():
 
 def test_second_lap_graph_large_separators():
     """A second lap along the same corridor: every 10th pose also sees the pose 1 500 key frames earlier, so loop closures span every
-    index cut of the time dissection (csrc/ordering.cpp split_by_index) and the top separators are an order of magnitude larger than
+    index cut of the time dissection (csrc/ordering_cuts.cpp split_by_index) and the top separators are an order of magnitude larger than
     the look-back band (tools/symstats FGO_LAPS: 5 x the fill of the plain graph) -- wide row structures, long update lists and hub-like
     targets on a pose graph.  3 x optimize(2) against the oracle: chi2 trajectory 1e-8, lambda 1e-6, final chi2 1e-8."""
     g = synth(6000, 5, 0, seed=5)

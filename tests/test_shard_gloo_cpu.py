@@ -55,7 +55,7 @@ def _banded(n, band, rng, closures=0.0, span=None, drop=0.0):
 
 @pytest.mark.parametrize("case", ["chain", "band10", "closures", "laps", "pieces", "tiny", "shuffled"])
 def test_time_dissection_orderings_are_usable(case):
-    """Round 5's index cuts (csrc/ordering.cpp split_by_index: vertex index = time when >= 90 % of the edges lie inside a narrow index
+    """Round 5's index cuts (csrc/ordering_cuts.cpp split_by_index: vertex index = time when >= 90 % of the edges lie inside a narrow index
     band) and the level-structure dissection they replace, through the host-only decomposition (ordering + symbolic phase + domain
     assignment, no device): every graph shape below must come back with a valid assignment -- no edge between two domains, every
     rank used when the graph is large enough -- whatever mode the band test selects."""

@@ -1,7 +1,8 @@
 """Every table of the symbolic phase, to the bit: `tools/symstats` with FGO_DIGEST=1 prints a digest of every member of `struct Symbolic`
-and tests/golden/symbolic_digests.json holds what the commit named in that file gave (tests/symbolic_digest.py: the case list and the
-writer).  The member names are read from csrc/fgo_internal.hpp, so a table added later cannot escape the comparison.  CPU only."""
-import json
+and tests/golden/symbolic_digests.json and ordering_digests.json hold what the commits named in those files gave (tests/symbolic_digest.py: the case list and the
+writer).  The member names are read from csrc/fgo_internal.hpp, so a table added later cannot escape the comparison.  The tool also
+prints which paths of the nested dissection the order came by: they must not depend on the thread count, and a case that pins one of
+those paths must take it.  CPU only."""
 import os
 import re
 
@@ -34,8 +35,7 @@ def symbolic_members():
 
 @pytest.fixture(scope="module")
 def golden():
-    with open(sd.GOLDEN) as f:
-        return json.load(f)
+    return sd.load_golden()
 
 
 @pytest.fixture(scope="module")
@@ -51,7 +51,7 @@ def test_the_header_parser_finds_the_members():
 
 
 def test_the_golden_file_covers_the_cases_and_the_code_that_moves(golden):
-    assert re.fullmatch(r"[0-9a-f]{40}", golden["written_at_commit"])
+    assert len(golden["written_at_commit"]) == 2 and all(re.fullmatch(r"[0-9a-f]{40}", c) for c in golden["written_at_commit"])
     assert sorted(golden["cases"]) == sorted(CASES)
     g = golden["cases"]
     assert g["star"]["digest"]["n_scratch"] > 0                                           # hub pieces
@@ -66,11 +66,20 @@ def test_tables_equal_the_golden_digests(golden, tool, name):
     exe, edge_files = tool
     want = golden["cases"][name]
     members = [m for m in symbolic_members() if m not in EXEMPT]
+    paths = []
     for threads in sd.THREADS:
         got = sd.run_case(exe, CASES[name], edge_files, threads)
+        paths.append(got["path"])
         missing = [m for m in members if m not in got["digest"]]
         assert not missing, "tools/symstats prints no digest of %s" % missing
         assert sorted(want["digest"]) == sorted(members), "the golden file does not hold the members of struct Symbolic"
         differ = [m for m in members if got["digest"][m] != want["digest"][m]]
         assert not differ, "%s, %d host threads: %s differ from the golden digests" % (name, threads, differ)
         assert got["count"] == want["count"]
+    assert len(paths[0]) >= 13 and all(p == paths[0] for p in paths), "the paths of the dissection depend on the thread count: %s" % paths
+    for path, least in sd.REACHES.get(re.sub(r"-world\d+$", "", name), {}).items():
+        assert paths[0][path] >= least, "%s does not take the path it pins: %s = %d" % (name, path, paths[0][path])
+
+
+def test_the_path_table_names_cases():
+    assert set(sd.REACHES) <= set(CASES) and set(sd.EDGE_CASES) <= set(sd.REACHES)

@@ -1,7 +1,7 @@
-"""Host structure phase (ordering.cpp + symbolic.cpp) on several host threads: the elimination order, the update lists
-and the task / panel schedule must be the same for every thread count (the parallel top of the nested dissection emits
-in post-order, the update lists are generated per target column with no shared cursors).  CPU only: builds the
-developer tool tools/symstats.cpp, which links the two sources without the device part."""
+"""Host structure phase (ordering.cpp + symbolic.cpp and their phase files) on several host threads: the elimination order, the update
+lists and the task / panel schedule must be the same for every thread count (the parallel top of the nested dissection --
+ordering_tree.cpp order_all -- emits in post-order, the update lists are generated per target column with no shared cursors).  CPU
+only: builds the developer tool tools/symstats.cpp, which links the two drivers without the device part."""
 import os
 import subprocess
 
@@ -80,7 +80,7 @@ def _levels(exe, n, lookback, loops, extra_env):
 def test_time_dissection_under_recovered_labels(symstats, n):
     """VERDICT r5 next #4a: a band graph (predecessor + look-back edges, no loop closures) whose vertex ids are NOT creation order -- a .g2o
     file need not number its vertices in time -- gets the index-cut dissection too: one Cuthill-McKee pass recovers the order (ordering.cpp
-    nested_dissection), the same band test decides, and the structure comes out as that of the creation-order graph (levels within one,
+    cuthill_mckee_labels), the same band test decides, and the structure comes out as that of the creation-order graph (levels within one,
     fill and block updates within 1 %); with the recovery switched off the relabelled graph falls back to the level structures."""
     lv0, nnz0, ops0 = _levels(symstats, n, 10, 0, {})
     for seed in ("1", "2"):

@@ -9,13 +9,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def build_symstats():
-    """tools/symstats: the host structure phase (ordering.cpp + symbolic.cpp, whose phase files the tool includes through
-    tools/symbolic_phases.hpp) without the device part.  Built when missing or older than a source or a header it reads; returns the
+    """tools/symstats: the host structure phase (ordering.cpp + symbolic.cpp, whose phase files -- ordering_*.cpp, symbolic_*.cpp -- the
+    tool includes through tools/symbolic_phases.hpp) without the device part.  Built when missing or older than a source or a header it reads; returns the
     path of the program."""
     csrc = os.path.join(ROOT, "graph_slam_amd", "csrc")
     exe = os.path.join(ROOT, "tools", "symstats")
     src = [os.path.join(ROOT, "tools", "symstats.cpp")] + [os.path.join(csrc, f) for f in ("symbolic.cpp", "ordering.cpp", "synth.cpp")]
-    deps = src + glob.glob(os.path.join(csrc, "symbolic_*.cpp")) + glob.glob(os.path.join(csrc, "*.hpp"))
+    deps = src + glob.glob(os.path.join(csrc, "symbolic_*.cpp")) + glob.glob(os.path.join(csrc, "ordering_*.cpp")) + glob.glob(os.path.join(csrc, "*.hpp"))
     deps += [os.path.join(ROOT, "tools", "symbolic_phases.hpp"), os.path.join(ROOT, "include", "fgo.h")]
     if not os.path.exists(exe) or any(os.path.getmtime(f) > os.path.getmtime(exe) for f in deps):
         subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", "-I" + ROOT, "-o", exe] + src, check=True, cwd=os.path.join(ROOT, "tools"))

@@ -7,7 +7,7 @@
 #include <algorithm>
 #include "../include/fgo.h"
 #include "../graph_slam_amd/csrc/fgo_internal.hpp"
-#include "symbolic_phases.hpp"     // the phase files of build_symbolic: not on the build line
+#include "symbolic_phases.hpp"     // the phase files of build_symbolic and of the ordering: not on the build line
 using namespace fgo;
 static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // FGO_DIGEST=1: one line per member of struct Symbolic (tests/test_symbolic_digest_cpu.py reads the member names from fgo_internal.hpp and
@@ -21,7 +21,7 @@ template <class V> static void digest_vec(const char *name, const V &v) {
   f.mix(v.data(), v.size() * sizeof(v[0]));
   printf("digest %s %zu %016llx\n", name, v.size(), (unsigned long long)f.h);
 }
-static void print_digests(const Symbolic &S) {
+static void print_digests(const Symbolic &S, const OrderingStats &paths) {
 #define DV(m) digest_vec(#m, S.m)
 #define DS(m) printf("digest %s %lld\n", #m, (long long)S.m)
   DS(nb); DV(perm); DV(iperm); DV(parent); DV(colptr); DV(rowidx); DV(blkcol);
@@ -51,6 +51,8 @@ static void print_digests(const Symbolic &S) {
     generic += !S.level_panel[l] && !S.level_leaf[l] && S.level_ptr[l + 1] > S.level_ptr[l];
   }
   printf("count leaf_levels %d\ncount generic_levels %d\n", leaf, generic);
+  // which paths of the nested dissection the order came by (not part of the golden file: the test holds each case to the path it is there for)
+  for (int i = 0; i < ND_PATHS; ++i) printf("path %s %lld\n", ORDERING_PATH_NAMES[i], (long long)paths.n[i]);
 }
 int main(int argc, char **argv) {
   int64_t N = argc > 1 ? atoll(argv[1]) : 10000;
@@ -98,17 +100,18 @@ int main(int argc, char **argv) {
   printf("unique offdiag blocks %zu\n", pr.size());
   std::vector<int> perm; OrderingOptions opt; opt.leaf = leaf; opt.time_side = tune("nd_time_side", opt.time_side); opt.time_weight = tune("nd_time_weight", opt.time_weight);
   if (std::getenv("FGO_ND_TWICE")) { std::vector<int> p2; t0 = now(); nested_dissection(g, opt, p2); printf("ND (first of two) %.3fs\n", now() - t0); }
-  t0 = now(); nested_dissection(g, opt, perm); printf("ND %.3fs (perm %zu)\n", now() - t0, perm.size());
+  OrderingStats paths;
+  t0 = now(); nested_dissection(g, opt, perm, &paths); printf("ND %.3fs (perm %zu)\n", now() - t0, perm.size());
   if (const char *pf = std::getenv("FGO_PERM")) {       // an ordering from outside (prototypes): int32 perm[n], perm[k] = vertex eliminated k-th
     FILE *f = fopen(pf, "rb"); std::vector<int> p2(n);
     if (!f || fread(p2.data(), 4, n, f) != (size_t)n) { fprintf(stderr, "cannot read %s\n", pf); return 2; }
     fclose(f); perm.swap(p2); printf("ordering read from %s\n", pf);
   }
   const int world = std::getenv("FGO_WORLD") ? atoi(std::getenv("FGO_WORLD")) : 1;
-  if (world > 1) { opt.bal_w = 8.0; nested_dissection(g, opt, perm); }       // (the product's distributed-mode balance weight)
+  if (world > 1) { opt.bal_w = 8.0; paths = OrderingStats(); nested_dissection(g, opt, perm, &paths); }       // (the product's distributed-mode balance weight)
   const bool analyse_only = std::getenv("FGO_ANALYSE_ONLY") != nullptr;
   Symbolic S; t0 = now(); build_symbolic(g, perm, limit, argc > 6 ? atoll(argv[6]) : limit, S, world, analyse_only); printf("symbolic %.2fs\n", now() - t0);
-  if (std::getenv("FGO_DIGEST")) { print_digests(S); return 0; }
+  if (std::getenv("FGO_DIGEST")) { print_digests(S, paths); return 0; }
   if (analyse_only) {                                    // (the sections below read tables that were not built)
     printf("nnzL blocks %lld nops %lld etree_height %d max_col_blocks %d tasks %zu levels %zu\n", (long long)S.nnzL, (long long)S.nops, S.etree_height, S.max_col_blocks, S.task_ptr.size() - 1, S.level_ptr.size() - 1);
     return 0;
