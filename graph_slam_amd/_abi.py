@@ -294,6 +294,7 @@ def _prototypes():
         "fgo_vro_ransac_batch": [i, i64, i64p, dp, dp, P(VroParams), dp, dp, dp, u8p, i32p, P(VroResult)],
         "fgo_debug_vro_waves": [i],
         "fgo_debug_vro_kernel_ms": (d, []),
+        "fgo_debug_grid_cap": [i],
         "fgo_match_params_default": (None, [P(MatchParams)]),
         "fgo_match_features_batch": [i, i64, i64p, u8p, dp, dp, i64, i64p, i64p, dp, u8p, P(MatchParams), P(MatchResult), i64p, i32p,
                                      i32p, i32p, u8p, i64p, i64p, i64p, dp, dp, dp, dp, i32p],

@@ -13,7 +13,7 @@ PKG = os.path.join(ROOT, "graph_slam_amd")
 CSRC = os.path.join(PKG, "csrc")
 LIBFGO = os.path.join(PKG, "libfgo.so")
 
-FGO_SOURCES = ["fgo_core.cpp", "host_alloc.cpp", "fgo_structure.cpp", "structure_pairs.cpp", "structure_tables.cpp", "structure_ba.cpp", "structure_upload.cpp", "structure_grow.cpp", "fgo_lm.cpp", "fgo_isam2.cpp", "isam_dirty.cpp", "fgo_dist.cpp", "fgo_inspect.cpp", "fgo_marginals.cpp", "synth.cpp", "ordering.cpp", "ordering_cuts.cpp", "ordering_leaves.cpp", "ordering_tree.cpp", "symbolic.cpp", "symbolic_pattern.cpp", "symbolic_schedule.cpp", "symbolic_lists.cpp", "symbolic_panels.cpp", "symbolic_riders.cpp", "imu_preint.cpp", "kernels.hip", "kernels_factor.hip", "kernels_solve.hip", "launch_select.cpp", "kernels_gtsam.hip", "kernels_ba.hip", "kernels_sinv.hip", "kernels_gate.hip", "kernels_plane_gate.hip", "preint_kernel.hip", "kernels_two_view.hip", "kernels_plane_check.hip", "kernels_imu_check.hip", "chi2_quantile.cpp", "kernels_vro_ransac.hip", "kernels_plane_extract.hip", "kernels_plane_propagate.hip", "kernels_feature_match.hip", "kernels_place.hip", "kernels_depth_align.hip", "map_cell_index.hip", "kernels_map_fuse.hip", "kernels_map_clean.hip", "kernels_map_normals.hip", "kernels_map_render.hip"]
+FGO_SOURCES = ["fgo_core.cpp", "host_alloc.cpp", "fgo_structure.cpp", "structure_pairs.cpp", "structure_tables.cpp", "structure_ba.cpp", "structure_upload.cpp", "structure_grow.cpp", "fgo_lm.cpp", "fgo_isam2.cpp", "isam_dirty.cpp", "fgo_dist.cpp", "fgo_inspect.cpp", "fgo_marginals.cpp", "synth.cpp", "ordering.cpp", "ordering_cuts.cpp", "ordering_leaves.cpp", "ordering_tree.cpp", "symbolic.cpp", "symbolic_pattern.cpp", "symbolic_schedule.cpp", "symbolic_lists.cpp", "symbolic_panels.cpp", "symbolic_riders.cpp", "imu_preint.cpp", "kernels.hip", "kernels_factor.hip", "kernels_solve.hip", "launch_select.cpp", "kernels_gtsam.hip", "kernels_ba.hip", "kernels_sinv.hip", "kernels_gate.hip", "kernels_plane_gate.hip", "preint_kernel.hip", "kernels_two_view.hip", "kernels_plane_check.hip", "kernels_imu_check.hip", "chi2_quantile.cpp", "kernels_vro_ransac.hip", "kernels_plane_extract.hip", "kernels_plane_propagate.hip", "kernels_feature_match.hip", "kernels_place.hip", "kernels_depth_align.hip", "batch_call.cpp", "map_cell_index.hip", "kernels_map_fuse.hip", "kernels_map_clean.hip", "kernels_map_normals.hip", "kernels_map_render.hip"]
 
 
 def _hipcc():

@@ -56,10 +56,13 @@ struct Arena {
   template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(base + off); }
 };
 
-// the workgroups of a launch over `items` items, per_group to a workgroup: at least one and at most 2^20, the kernels stride beyond that
+// the workgroups of a launch over `items` items, per_group to a workgroup: at least one and at most grid_cap() -- 2^20 unless
+// fgo_debug_grid_cap lowered it (batch_call.cpp) -- the kernels stride beyond that
+constexpr unsigned GRID_CAP_DEFAULT = 1u << 20;
+unsigned grid_cap();
 inline unsigned grid_for(unsigned long long items, unsigned per_group) {
-  const unsigned long long g = (items + per_group - 1) / per_group;
-  return (unsigned)(g < 1 ? 1 : g > (1u << 20) ? (1u << 20) : g);
+  const unsigned long long g = (items + per_group - 1) / per_group, cap = grid_cap();
+  return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
 }
 
 // The kernel time a debug hook reports: a pair of events on the null stream around the launches of a call.  ms() does not wait: it

@@ -544,6 +544,11 @@ int fgo_vro_ransac_batch(int device, int64_t n_pairs, const int64_t *match_ptr /
  * the kernel time of the last call by HIP events, ms */
 int fgo_debug_vro_waves(int waves);
 double fgo_debug_vro_kernel_ms(void);
+/* development: the largest grid of the next launches of the capped-grid kernels (map fusion, cleaning, normals and rendering, the
+ * cell index, vocabulary training and place query), which stride over whatever the grid does not cover: 1 .. 2^20; 0 = the default,
+ * 2^20; any other value changes nothing.  Returns the value in force.  Results do not depend on it; tests lower it to run every
+ * stride loop past its grid at small shapes. */
+int fgo_debug_grid_cap(int cap);
 
 /* Descriptor matching of key-frame pairs, batched: the step that PRODUCES the matched 3-D features the calls above start from --
  * CCameraNode::matchNodePair before its RANSAC (g2o/g2o_graph.cpp:174,210-211, gtsam/gtsam_graph.cpp:1730-1731) and the pose-guided
